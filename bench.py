@@ -1,6 +1,7 @@
 """Benchmark: rays/s of the hierarchical render path at 800x800, 64 coarse + 128 fine samples.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--scene chair|hotdog]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 `python bench.py --gpus N` (N > 1, WORLD_SIZE unset) starts the N ranks itself: it runs
@@ -21,6 +22,13 @@ rank with one RCCL all-gather of [r,g,b,depth] per ray (frames.py).
   --scaling strong: one frame per step sharded over the N ranks (BASELINE config 4 with
                     --scene hotdog: one 800x800 frame ray-chunk sharded across the GPUs).
 Rank 0 prints one JSON line.  value = rays of all ranks / max-over-ranks wall time.
+A plain run sets up, warms up, times the K steps and prints that line; the cpu_baseline, f32_exact
+and train legs below run only with --full (their keys are null without it).
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned, the
+reassembled rgb [rays, 3] and depth [rays] of its frames, as DIR/rgb.npy and DIR/depth.npy
+(float32; past 64 MB in all, a fixed seeded sample of the rays with their indices in
+DIR/ray_index.npy).  Poses, weights, embedding and the in-kernel draws (keyed by the step index
+and the global ray index) depend on the arguments alone, so two builds compare output for output.
 
 roofline: the dominant kernel is the fused PE->MLP kernel.  Its algorithmic work is 1,048,832
 FLOP per evaluated sample; each step launches it twice (B*64 and B*128
@@ -34,12 +42,12 @@ MLP launch inside nerf_render_rays (nerf_profile_mlp_begin/_end; no change to wh
         MFMA FLOP (6144 v_mfma_f32_16x16x32_f16 per 32 samples, the FLOP of 3072 32x32x16) against
         2516.8 TFLOP/s;
   f32   (mlp_kernel): v_mfma_f32_32x32x2_f32, peak 157.3 TFLOP/s.
-cpu_baseline: the oracle (PyTorch-CPU restatement, oracle/nerf_oracle.py) timed on a
+cpu_baseline (--full): the oracle (PyTorch-CPU restatement, oracle/nerf_oracle.py) timed on a
 bounded sample of the same workload on this host's cores (rank 0, N=1 only); the GPU renders
 the same rays with the same uniforms and the line reports the PSNR of its rgb against the
 oracle's (the metric's "PSNR vs reference").  The oracle evaluates all 256 MLP points per ray
 (the reference's formulation) where the GPU evaluates 192 (coarse reuse, bit-identical).
-The same line carries two more legs, measured in the same process after the headline steps:
+With --full the same line carries two more legs, measured in the same process after the headline steps:
   f32_exact (N = 1): --f32-steps frames of the headline workload on the exact-f32 MLP
         (mlp_kernel, v_mfma_f32_32x32x2_f32: the reference's arithmetic), roofline against 157.3;
   train (every rank, data parallel over the same group): bench_train.measure, BASELINE config 5 —
@@ -96,6 +104,10 @@ def parse():
     p.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                    help="weak: one frame per rank per step; strong: one frame per step over all ranks")
     p.add_argument("--arith", default="f16x3", choices=("f16x3", "f32"), help="MLP MFMA arithmetic")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's rgb and depth to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the CPU baseline / PSNR, exact-f32 and training legs (each has its --no-* switch)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=15.0, help="target length of the CPU baseline sample")
     p.add_argument("--dry-run", action="store_true", help="CPU/gloo rehearsal of the N-rank plumbing (no GPU)")
@@ -248,7 +260,8 @@ def dry_run(args, world, rank):
 
 def time_render(step, first, steps, group):
     """steps timed calls of step(first + i) between barriers + synchronize; returns (this rank's
-    seconds, the MLP launches [(ms, samples)] timed by libnerfmi's events on the MLP's stream)."""
+    seconds, the MLP launches [(ms, samples)] timed by libnerfmi's events on the MLP's stream,
+    what the last call returned)."""
     from nerfmi import _lib
     torch.cuda.synchronize()
     if group is not None:
@@ -257,13 +270,35 @@ def time_render(step, first, steps, group):
     torch.cuda.synchronize()
     _lib.profile_mlp_begin(cap)
     t0 = time.perf_counter()
+    out = None
     for i in range(steps):
-        step(first + i)
+        out = None                       # the previous step's frames are released before the next, as unkept
+        out = step(first + i)
     torch.cuda.synchronize()
     if group is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    return elapsed, _lib.profile_mlp_end(cap)
+    return elapsed, _lib.profile_mlp_end(cap), out
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, rgb, depth):
+    """DIR/rgb.npy [n, 3] and DIR/depth.npy [n], float32: every ray of the step, or (past
+    DUMP_MAX_BYTES) the rays of DIR/ray_index.npy, a sorted sample drawn with a fixed seed."""
+    import numpy as np
+    rgb = rgb.detach().reshape(-1, 3).float().cpu().numpy()
+    depth = depth.detach().reshape(-1).float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    n = depth.shape[0]
+    keep = DUMP_MAX_BYTES // (4 * 4 + 8)                   # r, g, b, depth as float32 + one float64 index
+    if n * 16 > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        np.save(os.path.join(path, "ray_index.npy"), idx.astype(np.float64))
+        rgb, depth = rgb[idx], depth[idx]
+    np.save(os.path.join(path, "rgb.npy"), rgb)
+    np.save(os.path.join(path, "depth.npy"), depth)
 
 
 def mlp_roofline(launches, arith):
@@ -308,11 +343,14 @@ def main():
     def step(i):
         rgb, depth = frames.render_path_frames(model, poses, H, W, focal, 2.0, 6.0, N_COARSE, N_FINE,
                                                appearance_embedding=app, perturb=True, hierarchical=True, seed=i)
-        return rgb
+        return rgb, depth
 
     for i in range(args.warmup):
         step(i)
-    elapsed, launches = time_render(step, args.warmup, args.steps, group)
+    elapsed, launches, last = time_render(step, args.warmup, args.steps, group)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
+    del last
     rank_ms = bench_train.gather_rank_ms(1e3 * elapsed / args.steps, group)
     elapsed = max(rank_ms) * args.steps * 1e-3           # max over ranks
 
@@ -325,10 +363,10 @@ def main():
 
     # --- exact-f32 leg (rank 0 alone, N = 1): the reference's arithmetic, v_mfma_f32_32x32x2_f32
     f32_exact = None
-    if world == 1 and not args.no_f32 and args.arith != "f32":
+    if args.full and world == 1 and not args.no_f32 and args.arith != "f32":
         nerfmi.set_mlp_arith("f32")
         step(10_000)                                       # warmup under the f32 kernel
-        e32, l32 = time_render(step, 10_001, args.f32_steps, None)
+        e32, l32, _ = time_render(step, 10_001, args.f32_steps, None)
         nerfmi.set_mlp_arith(args.arith)
         a32, p32, k32, _ = mlp_roofline(l32, "f32")
         f32_exact = {"value": B * len(poses) * args.f32_steps / e32, "unit": "rays/s", "steps": args.f32_steps,
@@ -341,7 +379,7 @@ def main():
 
     # --- training leg (BASELINE config 5), every rank: data parallel over the same group
     train = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         # (10 untimed steps: after 3 the step still runs ~2 % slow, profiles/r05/train_warmup.log)
         targs = argparse.Namespace(steps=args.train_steps, warmup=10, batch=4096, arith=args.arith,
                                    no_cpu_baseline=args.no_cpu_baseline, cpu_seconds=8.0)
@@ -399,7 +437,7 @@ def main():
             "f32_exact": f32_exact,
             "train": train,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             @torch.no_grad()
             def gpu_render(o, d, a, t_rand, u_rand):
                 rgb, depth, _ = nerfmi.render_rays(model, o.to(dev), d.to(dev), 2.0, 6.0, N_COARSE, N_FINE,

@@ -19,7 +19,7 @@ for step in "$@"; do
     pytest_all) run pytest_gpu 900 python -u -m pytest tests -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     pytest_new) run pytest_new 900 python -u -m pytest tests/test_gpu_autograd.py tests/test_gpu_shards.py -v -s -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     pytest_train) run pytest_train 600 python -m pytest tests/test_gpu_train.py -q -p no:cacheprovider ;;
-    bench) run bench 600 python bench.py --steps 5 --warmup 1 ;;
+    bench) run bench 600 python bench.py --full --steps 5 --warmup 1 ;;
     bench_f32) run bench_f32 600 python bench.py --steps 3 --warmup 1 --arith f32 --no-cpu-baseline ;;
     parity) run pytest_parity 600 python -u -m pytest tests/test_gpu_parity.py -x -v -s --timeout 120 --timeout-method thread -p no:cacheprovider ;;
     bench_train) run bench_train 600 python bench_train.py --steps 20 --warmup 3 ;;

@@ -81,6 +81,36 @@ def test_bench_train_gpus_8_plan():
     assert len(line["rank_ms"]) == 8
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 rgb [n, 3] and depth [n] of every ray while they fit the byte
+    limit (64 MB); past it the same sorted, seeded sample of rays on every call, with its indices."""
+    import numpy as np
+    import torch
+    import bench
+    assert bench.DUMP_MAX_BYTES == 64 * 2 ** 20
+    n = 1000
+    rgb = torch.arange(3 * n, dtype=torch.float32).reshape(10, 100, 3)
+    depth = torch.arange(n, dtype=torch.float32).reshape(10, 100)
+    bench.dump_outputs(str(tmp_path / "all"), rgb, depth)
+    assert sorted(os.listdir(tmp_path / "all")) == ["depth.npy", "rgb.npy"]
+    got = np.load(tmp_path / "all" / "rgb.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rgb.reshape(-1, 3).numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "depth.npy"), depth.reshape(-1).numpy())
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2400)          # 100 rays of 24 bytes
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), rgb, depth)
+    files = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert list(files) == ["depth.npy", "ray_index.npy", "rgb.npy"]
+    assert sum(a.nbytes for a in files.values()) <= 2400
+    idx = files["ray_index.npy"]
+    assert idx.dtype == np.float64 and idx.shape == (100,) and (np.diff(idx) > 0).all() and idx[-1] < n
+    assert files["depth.npy"].dtype == np.float32 and np.array_equal(files["depth.npy"], idx.astype(np.float32))
+    assert np.array_equal(files["rgb.npy"], rgb.reshape(-1, 3).numpy()[idx.astype(np.int64)])
+    for f, a in files.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f), a)
+
+
 def test_leftover_world_size_runs_alone():
     """A WORLD_SIZE left in the environment without a launcher's rendezvous marker does not make the
     bench wait on an env:// rendezvous: it runs as one process (nerfmi.launch.under_launcher)."""

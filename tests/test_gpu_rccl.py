@@ -46,7 +46,8 @@ def _json_line(stdout, prefix="{"):
 
 
 def test_bench_under_launcher_runs_on_rccl():
-    line = _json_line(_torchrun(["bench.py", "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]))
+    line = _json_line(_torchrun(["bench.py", "--gpus", "1", "--steps", "1", "--warmup", "0", "--full",
+                                 "--no-cpu-baseline"]))
     assert line["n_gpus"] == 1 and line["ranks"] == [0], line
     assert line["process_group"] == "nccl (RCCL)" and line["value"] > 0
 
