@@ -121,6 +121,19 @@ _SIGNATURES = {
                                       _V]),
     "nerf_effect_toon": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _V,
                                         _V, ctypes.c_size_t, _V]),
+    "nerf_effect_vignette": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, ctypes.c_double, _V, _V]),
+    "nerf_effect_cross_processing": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, _V]),
+    "nerf_effect_film_grain": (ctypes.c_int, [_V, _V, ctypes.c_int, ctypes.c_int, ctypes.c_double, _V, _V]),
+    "nerf_effect_posterize": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, ctypes.c_double, _V, _V]),
+    "nerf_effect_bloom": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _V, _V,
+                                         ctypes.c_size_t, _V]),
+    "nerf_effect_pencil_sketch": (ctypes.c_int, [_V, _V, ctypes.c_int, ctypes.c_int, ctypes.c_double, _V, _V,
+                                                 ctypes.c_size_t, _V]),
+    "nerf_effect_hologram": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _V] +
+                             [ctypes.c_int] * 6 + [_V, _V, _V, ctypes.c_size_t, _V]),
+    "nerf_gaussian_blur": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _V, _V,
+                                          ctypes.c_size_t, _V]),
+    "nerf_depth_percentile": (ctypes.c_int, [_V, _I64, _I64, ctypes.c_double, _V, _V, ctypes.c_size_t, _V]),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -12,6 +12,18 @@
 // Every pass is a per-pixel HBM-bound kernel on an 800x800 frame (a few MB): the work is in
 // global reductions (max/min for the normalisations, ordered-integer atomics, exact in any order)
 // and 3x3 / 9x9 stencils.
+//
+// The second half of the file adds Vignette, Cross Processing, Film Grain, Hologram, Posterize,
+// Bloom and Pencil Sketch.  Their numpy steps follow numpy 2's promotion rules operation for
+// operation (a Python float with a uint8 array is float64, with a float32 array float32, so
+// Vignette's distance field, Posterize's edge blend and Pencil Sketch's masked blend are float64
+// on the device too) and are pinned to the reference's own code by fixture F10
+// (tests/golden/make_effects_golden.py).  Their cv2 steps are parity unpinned, restated in
+// tests/effects_restated.py: cvtColor/Laplacian (exact in integers), Sobel (as Toon's),
+// cv2.divide, and two that are definitions of this project rather than OpenCV's code path:
+// GaussianBlur (float32 separable filter below; cv2's 8-bit path uses fixed-point coefficients and
+// may differ by a count) and addWeighted (float32 multiply, add, round half to even).
+// np.percentile (Pencil Sketch's background mask) is an exact radix select on the device.
 #include <math.h>
 #include <float.h>
 
@@ -296,6 +308,393 @@ __global__ void __launch_bounds__(256) toon_combine_kernel(const uint8_t* __rest
   }
 }
 
+
+// ============================================================== the seven further effects
+// Vignette (:161-186), Cross Processing (:271-298), Film Grain (:214-224), Hologram (:373-449),
+// Posterize (:300-318), Bloom (:146-159), Pencil Sketch (:226-269).  See the file header for what
+// is pinned to the reference and what is restated.
+
+__device__ __forceinline__ uint8_t to_u8d(double v) {     // np.clip(v, 0, 255).astype(np.uint8), float64
+  return (uint8_t)(int)fmin(fmax(v, 0.0), 255.0);
+}
+__device__ __forceinline__ int gray_px(const uint8_t* px) {   // cvtColor(RGB2GRAY), 14-bit fixed point
+  return (px[0] * 4899 + px[1] * 9617 + px[2] * 1868 + (1 << 13)) >> 14;
+}
+// (x - W//2)**2 + (y - H//2)**2 of np.ogrid (int64)
+__device__ __forceinline__ int64_t radial2(int y, int x, int H, int W) {
+  const int64_t dx = x - W / 2, dy = y - H / 2;
+  return dx * dx + dy * dy;
+}
+
+// Vignette: dist = sqrt(r2) / sqrt(cx^2 + cy^2), v = clip(1 - dist * strength, 0, 1), all float64
+// (np.sqrt of an int64 array); float32(img) * v is a float64 product stored into a float32 array.
+__global__ void __launch_bounds__(256) vignette_kernel(const uint8_t* __restrict__ img, int H, int W, double strength,
+                                                        uint8_t* __restrict__ out) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (int64_t)H * W) return;
+  const int y = (int)(p / W), x = (int)(p % W);
+  const int64_t cx = W / 2, cy = H / 2;
+  const double dist = sqrt((double)radial2(y, x, H, W)) / sqrt((double)(cx * cx + cy * cy));
+  const double v = fmin(fmax(1.0 - dist * strength, 0.0), 1.0);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[3 * p + c] = to_u8((float)((double)(float)img[3 * p + c] * v));
+}
+
+// Cross Processing: float32 channel gains 1.1 / 1.3 / 0.8 clipped to [0, 1], contrast
+// (f - 0.5) * 1.4 + 0.5, uint8 by truncation, then the float64 mask
+// clip(1.2 - r2 / (W/2)^2 * 0.4, 0, 1) and a second truncation.
+__global__ void __launch_bounds__(256) cross_kernel(const uint8_t* __restrict__ img, int H, int W,
+                                                     uint8_t* __restrict__ out) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (int64_t)H * W) return;
+  const int y = (int)(p / W), x = (int)(p % W);
+  const double half = (double)W / 2.0;
+  const double m = (double)radial2(y, x, H, W) / (half * half);
+  const double mask = fmin(fmax(1.2 - m * 0.4, 0.0), 1.0);
+  const float gain[3] = {1.1f, 1.3f, 0.8f};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float f = (float)img[3 * p + c] / 255.0f;
+    f = fminf(fmaxf(f * gain[c], 0.0f), 1.0f);
+    f = (f - 0.5f) * 1.4f + 0.5f;
+    const uint8_t r = to_u8(f * 255.0f);
+    out[3 * p + c] = (uint8_t)(int)((double)(float)r * mask);
+  }
+}
+
+// Film Grain: img + grain * amount in float32 (grain: float32 draws of N(0, 50), one per value).
+__global__ void __launch_bounds__(256) grain_kernel(const uint8_t* __restrict__ img, const float* __restrict__ grain,
+                                                     int64_t n, float amount, uint8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = to_u8((float)img[i] + grain[i] * amount);
+}
+
+// Posterize: float32 quantisation (as Toon's); edges where |Laplacian(gray)| > 20 (integers, exact);
+// there 255 * 0.3 + float64(q * 0.7f) in float64, elsewhere q.
+__global__ void __launch_bounds__(256) posterize_kernel(const uint8_t* __restrict__ img, int H, int W, float levels,
+                                                         uint8_t* __restrict__ out) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (int64_t)H * W) return;
+  const int y = (int)(p / W), x = (int)(p % W);
+  auto g = [&](int yy, int xx) { return gray_px(img + 3 * ((int64_t)reflect101(yy, H) * W + reflect101(xx, W))); };
+  const int lap = g(y - 1, x) + g(y, x - 1) + g(y, x + 1) + g(y + 1, x) - 4 * g(y, x);
+  const bool edge = (lap < 0 ? -lap : lap) > 20;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float q = floorf((float)img[3 * p + c] / 255.0f * levels) / levels * 255.0f;
+    out[3 * p + c] = to_u8d(edge ? 255.0 * 0.3 + (double)(q * 0.7f) : (double)q);
+  }
+}
+
+// ------------------------------------------------------------------ separable Gaussian blur
+// cv2.GaussianBlur(src, (k, k), 0) on uint8, 1 or 3 interleaved channels, odd k <= 63, restated
+// (cv2 is not installed: parity unpinned; cv2's 8-bit path uses fixed-point coefficients and may
+// differ by a count).  Coefficients: nerf_gaussian_blur's comment below.  Horizontal pass into a
+// float32 plane, vertical pass from it; each accumulates the taps in order i = 0..k-1 with one
+// multiply and one add rounding per tap; reflect-101 borders reflected repeatedly; the vertical
+// pass rounds half to even, saturates and stores uint8.  Both passes stage their inputs in an LDS
+// tile with the halo, so each input is read from memory once per tile, not once per tap.
+constexpr int kBlurMaxK = 63;
+struct BlurTaps {
+  int k;
+  float w[kBlurMaxK];
+};
+constexpr int kBlurTW = 256;     // horizontal pass: pixels of one row per block
+constexpr int kBlurCols = 64;    // vertical pass: 64 columns x 32 rows per block
+constexpr int kBlurRows = 32;
+enum { kSrcU8 = 0, kSrcInvGray = 1 };   // the pass reads the image, or 255 - gray(RGB) (Pencil Sketch)
+
+template <int C, int SRC>
+__global__ void __launch_bounds__(256) blur_h_kernel(const uint8_t* __restrict__ src, int H, int W, BlurTaps taps,
+                                                      float* __restrict__ mid) {
+  __shared__ float tile[(kBlurTW + kBlurMaxK - 1) * C];
+  __shared__ float sw[kBlurMaxK];
+  const int k = taps.k, r = k >> 1;
+  const unsigned nbx = (unsigned)((W + kBlurTW - 1) / kBlurTW);
+  const int y = (int)(blockIdx.x / nbx), x0 = (int)(blockIdx.x % nbx) * kBlurTW;
+  const int tw = min(kBlurTW, W - x0);
+  if ((int)threadIdx.x < k) sw[threadIdx.x] = taps.w[threadIdx.x];
+  const uint8_t* row = src + (int64_t)y * W * (SRC == kSrcInvGray ? 3 : C);
+  for (int j = threadIdx.x; j < tw + 2 * r; j += 256) {
+    const int xx = reflect101(x0 - r + j, W);
+    if (SRC == kSrcInvGray) {
+      tile[j] = (float)(255 - gray_px(row + 3 * xx));
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) tile[j * C + c] = (float)row[xx * C + c];
+    }
+  }
+  __syncthreads();
+  float* dst = mid + ((int64_t)y * W + x0) * C;
+  for (int e = threadIdx.x; e < tw * C; e += 256) {
+    float acc = 0.0f;
+    for (int i = 0; i < k; ++i) acc = acc + sw[i] * tile[e + i * C];
+    dst[e] = acc;
+  }
+}
+
+// What the vertical pass does with a blurred value b (uint8):
+//   kEpiStore   out = b
+//   kEpiBloom   cv2.addWeighted(img, 1, blur, beta, 0) restated: img + b * beta in float32 (separate
+//               multiply and add), rounded half to even, saturated
+//   kEpiSketch  Pencil Sketch from `b` = blur(255 - gray): sketch = cv2.divide(gray, 255 - b, 256)
+//               (0 where the divisor is 0, else rint(256 gray / divisor) saturated), the depth mask
+//               1 - clip((dn - thr) * 5, 0, 1) (float32; 1 without depth), then per channel
+//               float32(((1 - s) img + s sketch) * mask) [float64] + img * (1 - mask) [float32].
+enum { kEpiStore = 0, kEpiBloom = 1, kEpiSketch = 2 };
+struct BlurEpi {
+  int mode;
+  const uint8_t* img;
+  float beta;
+  const float* depth;
+  const unsigned* mm;
+  const float* thr;
+  double s, oms;
+};
+
+__global__ void __launch_bounds__(256) blur_v_kernel(const float* __restrict__ mid, int H, int64_t N, BlurTaps taps,
+                                                      BlurEpi epi, uint8_t* __restrict__ out) {
+  __shared__ float tile[kBlurRows + kBlurMaxK - 1][kBlurCols];
+  __shared__ float sw[kBlurMaxK];
+  const int k = taps.k, r = k >> 1;
+  const unsigned nbx = (unsigned)((N + kBlurCols - 1) / kBlurCols);
+  const int64_t c0 = (int64_t)(blockIdx.x % nbx) * kBlurCols;
+  const int y0 = (int)(blockIdx.x / nbx) * kBlurRows;
+  const int cw = (int)imin64(kBlurCols, N - c0), th = min(kBlurRows, H - y0);
+  const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+  if ((int)threadIdx.x < k) sw[threadIdx.x] = taps.w[threadIdx.x];
+  if (lx < cw)
+    for (int j = ly; j < th + 2 * r; j += 4) tile[j][lx] = mid[(int64_t)reflect101(y0 - r + j, H) * N + c0 + lx];
+  __syncthreads();
+  if (lx >= cw) return;
+  for (int yy = ly; yy < th; yy += 4) {
+    float acc = 0.0f;
+    for (int i = 0; i < k; ++i) acc = acc + sw[i] * tile[yy + i][lx];
+    const int b = (int)fminf(fmaxf(rintf(acc), 0.0f), 255.0f);
+    const int64_t e = (int64_t)(y0 + yy) * N + c0 + lx;
+    if (epi.mode == kEpiStore) {
+      out[e] = (uint8_t)b;
+    } else if (epi.mode == kEpiBloom) {
+      out[e] = (uint8_t)(int)fminf(fmaxf(rintf((float)epi.img[e] + (float)b * epi.beta), 0.0f), 255.0f);
+    } else {
+      const uint8_t* px = epi.img + 3 * e;
+      const int g = gray_px(px), div = 255 - b;
+      const double sk = div == 0 ? 0.0 : fmin(rint((double)(256 * g) / (double)div), 255.0);
+      float m = 1.0f;
+      if (epi.depth) {
+        const float dmax = ord2f(epi.mm[0]);
+        float dn = epi.depth[e];
+        if (dmax > 1.0f) dn = dn / dmax;
+        m = 1.0f - fminf(fmaxf((dn - epi.thr[0]) * 5.0f, 0.0f), 1.0f);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float v = (float)((epi.oms * (double)px[c] + epi.s * sk) * (double)m);
+        v = v + (float)px[c] * (1.0f - m);
+        out[3 * e + c] = to_u8(v);
+      }
+    }
+  }
+}
+
+static int launch_blur(const uint8_t* src, int H, int W, int C, int src_mode, const BlurTaps& taps, float* mid,
+                       const BlurEpi& epi, uint8_t* out, hipStream_t s) {
+  const unsigned hb = (unsigned)((W + kBlurTW - 1) / kBlurTW) * (unsigned)H;
+  if (src_mode == kSrcInvGray)
+    hipLaunchKernelGGL((blur_h_kernel<1, kSrcInvGray>), dim3(hb), dim3(256), 0, s, src, H, W, taps, mid);
+  else if (C == 1)
+    hipLaunchKernelGGL((blur_h_kernel<1, kSrcU8>), dim3(hb), dim3(256), 0, s, src, H, W, taps, mid);
+  else
+    hipLaunchKernelGGL((blur_h_kernel<3, kSrcU8>), dim3(hb), dim3(256), 0, s, src, H, W, taps, mid);
+  if (int rc = check_launch("blur_h_kernel")) return rc;
+  const int64_t N = (int64_t)W * C;
+  const unsigned vb = (unsigned)((N + kBlurCols - 1) / kBlurCols) * (unsigned)((H + kBlurRows - 1) / kBlurRows);
+  hipLaunchKernelGGL(blur_v_kernel, dim3(vb), dim3(256), 0, s, mid, H, N, taps, epi, out);
+  return check_launch("blur_v_kernel");
+}
+
+// ------------------------------------------------------------------------ exact percentile
+// Order statistics k0 <= k1 of x[i*stride], i < n, by radix select on the f2ord keys: four passes
+// of 8 bits from the top; each pass counts, per target, the digit of every key that matches the
+// target's prefix so far (LDS-private 256-bin histograms merged by integer atomics: exact and the
+// same in any order), then one small block walks the bins to the digit that holds the rank.
+struct SelectState {
+  unsigned hist[2][256];
+  unsigned prefix[2];
+  unsigned rank[2];
+  float value;
+};
+
+__global__ void select_init_kernel(SelectState* __restrict__ st, unsigned k0, unsigned k1) {
+  for (int i = threadIdx.x; i < 512; i += blockDim.x) (&st->hist[0][0])[i] = 0u;
+  if (threadIdx.x < 2) {
+    st->prefix[threadIdx.x] = 0u;
+    st->rank[threadIdx.x] = threadIdx.x ? k1 : k0;
+  }
+}
+
+__global__ void __launch_bounds__(256) select_hist_kernel(const float* __restrict__ x, int64_t n, int64_t stride,
+                                                           SelectState* __restrict__ st, int pass) {
+  __shared__ unsigned h[2][256];
+  h[0][threadIdx.x] = 0u;
+  h[1][threadIdx.x] = 0u;
+  __syncthreads();
+  const int shift = 24 - 8 * pass;
+  const unsigned himask = pass ? 0xffffffffu << (shift + 8) : 0u;
+  const unsigned p0 = st->prefix[0], p1 = st->prefix[1];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const unsigned key = f2ord(x[i * stride]);
+    const unsigned d = (key >> shift) & 255u;
+    if ((key & himask) == p0) atomicAdd(&h[0][d], 1u);
+    if ((key & himask) == p1) atomicAdd(&h[1][d], 1u);
+  }
+  __syncthreads();
+  if (h[0][threadIdx.x]) atomicAdd(&st->hist[0][threadIdx.x], h[0][threadIdx.x]);
+  if (h[1][threadIdx.x]) atomicAdd(&st->hist[1][threadIdx.x], h[1][threadIdx.x]);
+}
+
+__global__ void select_scan_kernel(SelectState* __restrict__ st, int pass) {
+  if (threadIdx.x < 2) {
+    const int t = threadIdx.x;
+    const unsigned rank = st->rank[t];
+    unsigned cum = 0u;
+    int d = 0;
+    for (; d < 255; ++d) {
+      const unsigned c = st->hist[t][d];
+      if (rank < cum + c) break;
+      cum += c;
+    }
+    st->prefix[t] |= (unsigned)d << (24 - 8 * pass);
+    st->rank[t] = rank - cum;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 512; i += blockDim.x) (&st->hist[0][0])[i] = 0u;
+}
+
+// numpy's "linear" interpolation in float32 between a = x_(k0) and b = x_(k1): a + (b - a) t, or
+// b - (b - a)(1 - t) where t >= 0.5 (np.percentile's _lerp).  With mm, the values are first divided
+// by the maximum when it exceeds 1 (the effects' depth normalisation: monotone, so the order
+// statistics of the normalised plane are the normalised order statistics).
+__global__ void select_finish_kernel(SelectState* __restrict__ st, const unsigned* __restrict__ mm, float t,
+                                     float* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  float a = ord2f(st->prefix[0]), b = ord2f(st->prefix[1]);
+  if (mm) {
+    const float mx = ord2f(mm[0]);
+    if (mx > 1.0f) {
+      a = a / mx;
+      b = b / mx;
+    }
+  }
+  const float d = b - a;
+  const float v = t >= 0.5f ? b - d * (1.0f - t) : a + d * t;
+  st->value = v;
+  if (out) out[0] = v;
+}
+
+// np.percentile's float32 index arithmetic (numpy 2: the quantile q / 100, the virtual index
+// (n - 1) * quantile and its fraction are all float32 for a float32 array).
+static void percentile_plan(int64_t n, double q, int64_t* k0, int64_t* k1, float* t) {
+  const float quant = (float)q / 100.0f;
+  const float last = (float)(n - 1);
+  const float v = last * quant;
+  if (v >= last) {
+    *k0 = *k1 = n - 1;
+    *t = 0.0f;
+    return;
+  }
+  const float lo = floorf(v);
+  *k0 = imin64((int64_t)lo, n - 1);
+  *k1 = imin64(*k0 + 1, n - 1);
+  *t = v - lo;
+}
+
+static int launch_percentile(const float* x, int64_t n, int64_t stride, double q, SelectState* st, const unsigned* mm,
+                             float* out, hipStream_t s) {
+  int64_t k0, k1;
+  float t;
+  percentile_plan(n, q, &k0, &k1, &t);
+  hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(256), 0, s, st, (unsigned)k0, (unsigned)k1);
+  if (int rc = check_launch("select_init_kernel")) return rc;
+  const int64_t blocks = (n + 255) / 256;
+  for (int pass = 0; pass < 4; ++pass) {
+    hipLaunchKernelGGL(select_hist_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, x, n,
+                       stride, st, pass);
+    if (int rc = check_launch("select_hist_kernel")) return rc;
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(64), 0, s, st, pass);
+    if (int rc = check_launch("select_scan_kernel")) return rc;
+  }
+  hipLaunchKernelGGL(select_finish_kernel, dim3(1), dim3(64), 0, s, st, mm, t, out);
+  return check_launch("select_finish_kernel");
+}
+
+// -------------------------------------------------------------------------------- Hologram
+// Scanline factor of each row (:385-393): line i darkens rows [int(i lh), int(min((i + 0.7) lh, H)))
+// by 0.85, lh = H / lines in float64; a row covered by several lines (H < lines) is multiplied
+// that many times, sequentially, in float32.
+__global__ void __launch_bounds__(256) holo_rows_kernel(int H, int lines, float* __restrict__ fac) {
+  const int y = blockIdx.x * blockDim.x + threadIdx.x;
+  if (y >= H) return;
+  const double lh = (double)H / (double)lines;
+  float f = 1.0f;
+  for (int i = 0; i < lines; ++i) {
+    const int ys = (int)((double)i * lh);
+    const double e = ((double)i + 0.7) * lh;
+    const int ye = (int)(e < (double)H ? e : (double)H);
+    if (y >= ys && y < ye) f = f * 0.85f;
+  }
+  fac[y] = f;
+}
+
+__global__ void __launch_bounds__(256) plane_dn_kernel(const float* __restrict__ depth, int64_t dstride, int64_t P,
+                                                        const unsigned* __restrict__ mm, float* __restrict__ out) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < P) out[p] = toon_dn(depth, p, dstride, ord2f(mm[0]));
+}
+
+// Column spans brightened by 1.5 (:443-447): [pos, min(pos + width, W)), three of them, applied in
+// order (overlaps multiply twice); by value, or read from device memory as int64 (pos, width) pairs.
+struct HoloSpans {
+  int pos[3], width[3];
+};
+
+// cyan tint (img / 255 times 0.8, 1.0, 0.2), scanlines, + edge glow (Sobel magnitude of the
+// normalised depth over its max, times 0.1, 0.6, 0.3) + noise, spans, * 255; float32 throughout.
+__global__ void __launch_bounds__(256) holo_kernel(const uint8_t* __restrict__ img, const float* __restrict__ mag,
+                                                    const unsigned* __restrict__ mm, const float* __restrict__ rowfac,
+                                                    const float* __restrict__ noise, int H, int W, HoloSpans spans,
+                                                    const int64_t* __restrict__ spans_dev, uint8_t* __restrict__ out) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (int64_t)H * W) return;
+  const int y = (int)(p / W), x = (int)(p % W);
+  float e = 0.0f;
+  if (mag) {
+    const float gmax = ord2f(mm[0]);
+    e = mag[p];
+    if (gmax > 0.0f) e = e / gmax;
+  }
+  float boost = 1.0f;   // 1.5^j, exact
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int64_t x0 = spans_dev ? spans_dev[2 * j] : spans.pos[j];
+    const int64_t x1 = imin64(x0 + (spans_dev ? spans_dev[2 * j + 1] : spans.width[j]), W);
+    if (x >= x0 && x < x1) boost = boost * 1.5f;
+  }
+  const float tint[3] = {0.8f, 1.0f, 0.2f}, glow[3] = {0.1f, 0.6f, 0.3f};
+  const float rf = rowfac[y];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float h = (float)img[3 * p + c] / 255.0f * tint[c] * rf;
+    h = (h + (mag ? e * glow[c] : 0.0f)) + noise[3 * p + c];
+    // h * 1.5 per covering span: multiplying by 1.5 up to three times in sequence
+    if (boost > 1.0f) h = h * 1.5f;
+    if (boost > 2.0f) h = h * 1.5f;
+    if (boost > 3.0f) h = h * 1.5f;
+    out[3 * p + c] = to_u8(h * 255.0f);
+  }
+}
+
 }  // namespace nerf
 
 using namespace nerf;
@@ -307,9 +706,18 @@ using namespace nerf;
 
 extern "C" {
 
+// Workspace: [0, 256) the reductions' max/min; three float planes (Toon uses two; the blur's
+// intermediate of a 3-channel image is three); kSelectBytes for the percentile's state; H floats
+// for Hologram's row factors.
+constexpr size_t kSelectBytes = 4096;
+static_assert(sizeof(SelectState) <= kSelectBytes, "percentile state");
+static size_t ws_plane(int H, int W) { return ((size_t)H * W * sizeof(float) + 255) & ~(size_t)255; }
+static size_t ws_select_off(int H, int W) { return 256 + 3 * ws_plane(H, W); }
+static size_t ws_rows_off(int H, int W) { return ws_select_off(H, W) + kSelectBytes; }
+
 size_t nerf_effect_workspace_bytes(int H, int W) {
   if (H <= 0 || W <= 0) return 0;
-  return 256 + 2 * (((size_t)H * W * sizeof(float) + 255) & ~(size_t)255);
+  return ws_rows_off(H, W) + (((size_t)H * sizeof(float) + 255) & ~(size_t)255);
 }
 
 int nerf_depth_normalize(const float* depth, int64_t n, float* out, void* workspace, size_t ws_bytes,
@@ -383,6 +791,169 @@ int nerf_effect_toon(const uint8_t* image, const float* depth, int64_t depth_str
   hipLaunchKernelGGL(toon_combine_kernel, dim3(blocks), dim3(256), 0, s, image, mag, mm, H, W, (float)levels,
                      (float)edge_strength, depth ? 0.05f : 0.1f, depth ? 1 : 0, out);
   return check_launch("toon_combine_kernel");
+}
+
+// cv2.getGaussianKernel(k, 0) as float32, on the host: OpenCV's fixed tables for k = 1, 3, 5, 7;
+// otherwise sigma = 0.3 ((k - 1) 0.5 - 1) + 0.8 and w_i = exp(-(i - (k-1)/2)^2 / (2 sigma^2)), in
+// double, divided by their double sum (added in order), then rounded to float32.
+static bool gaussian_taps(int k, BlurTaps* taps) {
+  if (k < 1 || k > kBlurMaxK || k % 2 == 0) return false;
+  static const float small[4][7] = {{1.f},
+                                    {.25f, .5f, .25f},
+                                    {.0625f, .25f, .375f, .25f, .0625f},
+                                    {.03125f, .109375f, .21875f, .28125f, .21875f, .109375f, .03125f}};
+  taps->k = k;
+  for (int i = 0; i < kBlurMaxK; ++i) taps->w[i] = 0.0f;
+  if (k <= 7) {
+    for (int i = 0; i < k; ++i) taps->w[i] = small[k / 2][i];
+    return true;
+  }
+  const double sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8;
+  double w[kBlurMaxK], sum = 0.0;
+  for (int i = 0; i < k; ++i) {
+    const double x = i - (k - 1) * 0.5;
+    w[i] = exp(-(x * x) / (2.0 * sigma * sigma));
+    sum += w[i];
+  }
+  for (int i = 0; i < k; ++i) taps->w[i] = (float)(w[i] / sum);
+  return true;
+}
+
+static bool blur_grid_fits(int H, int W) {   // block counts of both passes stay below 2^31
+  return ((int64_t)(W + kBlurTW - 1) / kBlurTW) * H < (1ll << 31) &&
+         (((int64_t)W * 3 + kBlurCols - 1) / kBlurCols) * ((H + kBlurRows - 1) / kBlurRows) < (1ll << 31);
+}
+
+int nerf_gaussian_blur(const uint8_t* image, int H, int W, int C, int k, uint8_t* out, void* workspace,
+                       size_t ws_bytes, nerf_stream_t stream) {
+  EREQUIRE(H > 0 && W > 0 && (C == 1 || C == 3) && blur_grid_fits(H, W), "nerf_gaussian_blur: H=%d W=%d C=%d", H, W, C);
+  BlurTaps taps;
+  EREQUIRE(gaussian_taps(k, &taps), "nerf_gaussian_blur: k=%d must be odd and within 1..%d", k, kBlurMaxK);
+  EREQUIRE(image && out && workspace && ws_bytes >= nerf_effect_workspace_bytes(H, W),
+           "nerf_gaussian_blur: null pointer or workspace too small");
+  BlurEpi epi = {};
+  epi.mode = kEpiStore;
+  return launch_blur(image, H, W, C, kSrcU8, taps, (float*)((char*)workspace + 256), epi, out, (hipStream_t)stream);
+}
+
+int nerf_effect_bloom(const uint8_t* image, int H, int W, int size, double strength, uint8_t* out, void* workspace,
+                      size_t ws_bytes, nerf_stream_t stream) {
+  EREQUIRE(H > 0 && W > 0 && blur_grid_fits(H, W), "nerf_effect_bloom: H=%d W=%d", H, W);
+  BlurTaps taps;
+  EREQUIRE(size < kBlurMaxK + 1 && gaussian_taps(size % 2 == 0 ? size + 1 : size, &taps),
+           "nerf_effect_bloom: bloom size %d (odd, or the next odd number) must be within 1..%d", size, kBlurMaxK);
+  EREQUIRE(image && out && workspace && ws_bytes >= nerf_effect_workspace_bytes(H, W),
+           "nerf_effect_bloom: null pointer or workspace too small");
+  BlurEpi epi = {};
+  epi.mode = kEpiBloom;
+  epi.img = image;
+  epi.beta = (float)strength;
+  return launch_blur(image, H, W, 3, kSrcU8, taps, (float*)((char*)workspace + 256), epi, out, (hipStream_t)stream);
+}
+
+int nerf_effect_vignette(const uint8_t* image, int H, int W, double strength, uint8_t* out, nerf_stream_t stream) {
+  EREQUIRE(H > 0 && W > 0, "nerf_effect_vignette: H=%d W=%d", H, W);
+  EREQUIRE(image && out, "nerf_effect_vignette: null pointer");
+  const int64_t P = (int64_t)H * W;
+  hipLaunchKernelGGL(vignette_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, image, H, W,
+                     strength, out);
+  return check_launch("vignette_kernel");
+}
+
+int nerf_effect_cross_processing(const uint8_t* image, int H, int W, uint8_t* out, nerf_stream_t stream) {
+  EREQUIRE(H > 0 && W > 0, "nerf_effect_cross_processing: H=%d W=%d", H, W);
+  EREQUIRE(image && out, "nerf_effect_cross_processing: null pointer");
+  const int64_t P = (int64_t)H * W;
+  hipLaunchKernelGGL(cross_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, image, H, W,
+                     out);
+  return check_launch("cross_kernel");
+}
+
+int nerf_effect_film_grain(const uint8_t* image, const float* noise, int H, int W, double amount, uint8_t* out,
+                           nerf_stream_t stream) {
+  EREQUIRE(H > 0 && W > 0, "nerf_effect_film_grain: H=%d W=%d", H, W);
+  EREQUIRE(image && noise && out, "nerf_effect_film_grain: null pointer");
+  const int64_t n = (int64_t)H * W * 3;
+  hipLaunchKernelGGL(grain_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, image, noise, n,
+                     (float)amount, out);
+  return check_launch("grain_kernel");
+}
+
+int nerf_effect_posterize(const uint8_t* image, int H, int W, double levels, uint8_t* out, nerf_stream_t stream) {
+  EREQUIRE(H > 0 && W > 0 && levels > 0.0, "nerf_effect_posterize: H=%d W=%d levels=%g", H, W, levels);
+  EREQUIRE(image && out, "nerf_effect_posterize: null pointer");
+  const int64_t P = (int64_t)H * W;
+  hipLaunchKernelGGL(posterize_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, image, H, W,
+                     (float)levels, out);
+  return check_launch("posterize_kernel");
+}
+
+int nerf_depth_percentile(const float* depth, int64_t n, int64_t stride, double q, float* out, void* workspace,
+                          size_t ws_bytes, nerf_stream_t stream) {
+  EREQUIRE(n >= 1 && n < (1ll << 31) && stride >= 1 && q >= 0.0 && q <= 100.0,
+           "nerf_depth_percentile: n=%lld stride=%lld q=%g", (long long)n, (long long)stride, q);
+  EREQUIRE(depth && out && workspace && ws_bytes >= kSelectBytes,
+           "nerf_depth_percentile: null pointer or workspace < %zu B", kSelectBytes);
+  return launch_percentile(depth, n, stride, q, (SelectState*)workspace, nullptr, out, (hipStream_t)stream);
+}
+
+int nerf_effect_pencil_sketch(const uint8_t* image, const float* depth, int H, int W, double strength, uint8_t* out,
+                              void* workspace, size_t ws_bytes, nerf_stream_t stream) {
+  EREQUIRE(H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && blur_grid_fits(H, W), "nerf_effect_pencil_sketch: H=%d W=%d",
+           H, W);
+  EREQUIRE(image && out && workspace && ws_bytes >= nerf_effect_workspace_bytes(H, W),
+           "nerf_effect_pencil_sketch: null pointer or workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t P = (int64_t)H * W;
+  unsigned* mm = (unsigned*)workspace;
+  SelectState* st = (SelectState*)((char*)workspace + ws_select_off(H, W));
+  if (depth) {   // 70th percentile of the normalised depth (:249-254), kept on the device
+    if (int rc = launch_minmax(depth, P, 1, mm, s)) return rc;
+    if (int rc = launch_percentile(depth, P, 1, 70.0, st, mm, nullptr, s)) return rc;
+  }
+  BlurTaps taps;
+  gaussian_taps(21, &taps);
+  BlurEpi epi = {};
+  epi.mode = kEpiSketch;
+  epi.img = image;
+  epi.depth = depth;
+  epi.mm = mm;
+  epi.thr = &st->value;
+  epi.s = strength;
+  epi.oms = 1.0 - strength;
+  return launch_blur(image, H, W, 1, kSrcInvGray, taps, (float*)((char*)workspace + 256), epi, out, s);
+}
+
+int nerf_effect_hologram(const uint8_t* image, const float* depth, int64_t depth_stride, int H, int W, int lines,
+                         const float* noise, int x0, int w0, int x1, int w1, int x2, int w2,
+                         const int64_t* spans_device, uint8_t* out, void* workspace, size_t ws_bytes,
+                         nerf_stream_t stream) {
+  EREQUIRE(H > 0 && W > 0 && depth_stride >= 1 && lines >= 1 && lines <= 65536,
+           "nerf_effect_hologram: H=%d W=%d stride=%lld lines=%d", H, W, (long long)depth_stride, lines);
+  EREQUIRE(image && noise && out && workspace && ws_bytes >= nerf_effect_workspace_bytes(H, W),
+           "nerf_effect_hologram: null pointer or workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t P = (int64_t)H * W;
+  const unsigned blocks = (unsigned)((P + 255) / 256);
+  unsigned* mm = (unsigned*)workspace;
+  float* dn = (float*)((char*)workspace + 256);
+  float* mag = (float*)((char*)workspace + 256 + ws_plane(H, W));
+  float* rowfac = (float*)((char*)workspace + ws_rows_off(H, W));
+  int rc;
+  hipLaunchKernelGGL(holo_rows_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, s, H, lines, rowfac);
+  if ((rc = check_launch("holo_rows_kernel"))) return rc;
+  if (depth) {   // the maximum is over every channel (:407-409), then channel 0 is used (:412-413)
+    if ((rc = launch_minmax(depth, P * depth_stride, 1, mm, s))) return rc;
+    hipLaunchKernelGGL(plane_dn_kernel, dim3(blocks), dim3(256), 0, s, depth, depth_stride, P, mm, dn);
+    if ((rc = check_launch("plane_dn_kernel"))) return rc;
+    hipLaunchKernelGGL(sobel_kernel, dim3(blocks), dim3(256), 0, s, dn, H, W, mag);
+    if ((rc = check_launch("sobel_kernel"))) return rc;
+    if ((rc = launch_minmax(mag, P, 1, mm, s))) return rc;
+  }
+  const HoloSpans spans = {{x0, x1, x2}, {w0, w1, w2}};
+  hipLaunchKernelGGL(holo_kernel, dim3(blocks), dim3(256), 0, s, image, depth ? mag : nullptr, mm, rowfac, noise, H, W,
+                     spans, spans_device, out);
+  return check_launch("holo_kernel");
 }
 
 }  // extern "C"

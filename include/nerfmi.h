@@ -225,6 +225,51 @@ int nerf_effect_toon(const uint8_t* image, const float* depth, int64_t depth_str
                      double levels, double edge_strength, uint8_t* out, void* workspace,
                      size_t ws_bytes, nerf_stream_t stream);
 
+/* Seven more effects of the reference's PostProcessor, with numpy 2's arithmetic operation for
+ * operation (fixture F10); their cv2 steps are restated (tests/effects_restated.py), GaussianBlur
+ * and addWeighted as float32 definitions of this project (cv2's 8-bit fixed-point paths may differ
+ * by a count).  Same conventions as above; the per-pixel effects need no workspace.
+ *   vignette           (post_processor.py:161-186) float64 radial mask 1 - dist * strength.
+ *   cross_processing   (:271-298) channel gains, contrast, float64 radial mask.
+ *   film_grain         (:214-224) img + noise * amount; noise: H*W*3 device floats, the float32
+ *                      draws of N(0, 50) in the image's element order.
+ *   posterize          (:300-318) levels > 0 (used as float32); gray Laplacian edges > 20 blended.
+ *   bloom              (:146-159) blur of size `size` (even sizes use the next odd one, 1..63), then
+ *                      img + blur * strength.
+ *   pencil_sketch      (:226-269) gray / (255 - blur21(255 - gray)) * 256 blended by `strength`; with
+ *                      depth (H,W) the background beyond the 70th percentile of the normalised depth
+ *                      fades back to the image.
+ *   hologram           (:373-449) cyan tint, `lines` (1..65536) scanlines, Sobel edge glow of the
+ *                      normalised depth (its maximum over all depth_stride channels, then channel 0),
+ *                      noise (H*W*3 device floats, the float32 draws of N(0, 0.03)) and three column
+ *                      spans [x, min(x + w, W)) brightened by 1.5 in order: by value, or, when
+ *                      spans_device is not null, six int64 (x0, w0, x1, w1, x2, w2) in device memory.
+ *   gaussian blur      the blur by itself: uint8 (H,W,C), C = 1 or 3, odd k in 1..63; coefficients
+ *                      OpenCV's fixed tables for k <= 7, else exp(-(i-(k-1)/2)^2 / (2 sigma^2)),
+ *                      sigma = 0.3 ((k-1) 0.5 - 1) + 0.8, normalised in double, used as float32.
+ *   depth percentile   np.percentile(x, q), method "linear", of the n float32 values x[i*stride]
+ *                      (n < 2^31, 0 <= q <= 100), exact (radix select, numpy's float32 index and
+ *                      interpolation); out: one device float; workspace >= 4096 bytes. */
+int nerf_effect_vignette(const uint8_t* image, int H, int W, double strength, uint8_t* out,
+                         nerf_stream_t stream);
+int nerf_effect_cross_processing(const uint8_t* image, int H, int W, uint8_t* out, nerf_stream_t stream);
+int nerf_effect_film_grain(const uint8_t* image, const float* noise, int H, int W, double amount,
+                           uint8_t* out, nerf_stream_t stream);
+int nerf_effect_posterize(const uint8_t* image, int H, int W, double levels, uint8_t* out,
+                          nerf_stream_t stream);
+int nerf_effect_bloom(const uint8_t* image, int H, int W, int size, double strength, uint8_t* out,
+                      void* workspace, size_t ws_bytes, nerf_stream_t stream);
+int nerf_effect_pencil_sketch(const uint8_t* image, const float* depth, int H, int W, double strength,
+                              uint8_t* out, void* workspace, size_t ws_bytes, nerf_stream_t stream);
+int nerf_effect_hologram(const uint8_t* image, const float* depth, int64_t depth_stride, int H, int W,
+                         int lines, const float* noise, int x0, int w0, int x1, int w1, int x2, int w2,
+                         const int64_t* spans_device, uint8_t* out, void* workspace, size_t ws_bytes,
+                         nerf_stream_t stream);
+int nerf_gaussian_blur(const uint8_t* image, int H, int W, int C, int k, uint8_t* out, void* workspace,
+                       size_t ws_bytes, nerf_stream_t stream);
+int nerf_depth_percentile(const float* depth, int64_t n, int64_t stride, double q, float* out,
+                          void* workspace, size_t ws_bytes, nerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,8 +19,11 @@ teacher-rendered synthetic scene), data-parallel under torchrun; --iterations ov
 Config.num_iterations; checkpoints go to --save_dir (default 'checkpoints', the reference's
 train_nerf default, while its render mode looks for checkpoints_<scene>/ — a reference
 inconsistency kept as is).  --use_shader / --shader NAME applies a depth-aware effect of the
-reference's PostProcessor on the GPU (nerfmi.PostProcessor: "Fog", "Toon Shader", "Original") to
-each frame before it is written, with run.py:248's depth normalisation; the reference's
+reference's PostProcessor on the GPU (nerfmi.PostProcessor: "Fog", "Toon Shader", "Hologram",
+"Pencil Sketch", "Bloom", "Vignette", "Cross Processing", "Film Grain", "Posterize", "Original"; the
+other four names are refused) to each frame before it is written, with run.py:248's depth
+normalisation, on the frame's device tensors (Film Grain and Hologram draw their noise from
+numpy's global generator, as the reference does); the reference's
 interactive first-frame editor (tkinter) is not reproduced, so --shader names the effect
 (default with --use_shader alone: Fog).  Out of scope: video encoding (--mode
 video, --create_video; cv2 is absent).
@@ -157,10 +160,15 @@ def write_frame(output_dir, frame_idx, rgb, depth, save_depth=False, raw_output=
     applied to the written rgb image (not the raw one) after run.py:248's depth normalisation, both
     on the GPU (Fog: nerf_frame_fog, straight from the render outputs)."""
     from PIL import Image
-    fogged = None
+    shaded = None
     if shader == "Fog" and not raw_output:                    # run.py:233 + :248 + Fog in one GPU pass
         from nerfmi.post_processor import PostProcessor, frame_fog
-        fogged = frame_fog(rgb, depth, PostProcessor().params["fog_start"]).cpu().numpy()
+        shaded = frame_fog(rgb, depth, PostProcessor().params["fog_start"]).cpu().numpy()
+    elif shader and not raw_output:                           # run.py:233, :247-262 on the device tensors
+        from nerfmi.post_processor import PostProcessor, normalize_depth
+        processor = PostProcessor()
+        processor.current_effect = shader
+        shaded = processor.apply_effect((rgb * 255).to(torch.uint8), normalize_depth(depth)).cpu().numpy()
     rgb, depth = rgb.cpu(), depth.cpu()
     rgb_img = (rgb * 255).numpy().astype(np.uint8)            # truncation, run.py:233
     depth_img = depth.numpy()
@@ -171,13 +179,8 @@ def write_frame(output_dir, frame_idx, rgb, depth, save_depth=False, raw_output=
         Image.fromarray(rgb_img).save(os.path.join(raw_dir, f'rgb_{frame_idx:03d}.png'))
     if save_depth:
         np.save(os.path.join(raw_dir, f'depth_{frame_idx:03d}.npy'), depth_img)
-    if fogged is not None:
-        rgb_img = fogged
-    elif shader and not raw_output:                           # run.py:247-262
-        from nerfmi.post_processor import PostProcessor, normalize_depth
-        processor = PostProcessor()
-        processor.current_effect = shader
-        rgb_img = processor.apply_effect(rgb_img, normalize_depth(depth_img))
+    if shaded is not None:
+        rgb_img = shaded
     Image.fromarray(rgb_img).save(os.path.join(output_dir, f'rgb_{frame_idx:03d}.png'))
     import matplotlib
     matplotlib.use('Agg')
