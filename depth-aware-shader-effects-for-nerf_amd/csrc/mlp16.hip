@@ -42,7 +42,7 @@
 
 namespace nerf {
 
-#ifdef NERF_MLP16_STAMPS   // diagnostic build (scripts/microbench/mlp16_stamps.hip): per-wave segment clocks
+#ifdef NERF_MLP16_STAMPS   // diagnostic build: per-wave segment clocks (the render kernel's: mlp16s.hip STAMP16S)
 __device__ unsigned long long nerf16_stamps[65536][16];
 #define STAMP16(i)                                                                          \
   do {                                                                                      \

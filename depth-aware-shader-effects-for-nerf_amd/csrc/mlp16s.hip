@@ -36,11 +36,45 @@
 // (counted vmcnt + barrier, as stream16.h) after segment 0 and the chunk three ahead is DMA'd in
 // segments 1-3.  The previous layer's epilogue (the side work) runs a quarter (one 16 x 16 tile of one
 // sample tile: 4 values) per segment in the MFMA shadow, on mlp16's group schedule.
+//
+// Block loop.  The grid is one workgroup per CU; workgroup b runs the 128-sample blocks b, b + grid,
+// ...  Biases, constants and the rgb head are staged in LDS once per workgroup.  The weight ring does
+// not drain between blocks: the colour layer's chunk-steps fetch the wrapped stream's chunks 0-2 and
+// read chunk 0's first fragments, so a block starts at layer 0's first MFMA.  The next block's inputs
+// are loaded during layer 7, and its positional encoding and layer-0 operands are computed as side
+// work in the 32 segments of layer 7's group B and of the colour layer that carry no quarter.  Per
+// sample the arithmetic is the one-block kernel's, operation for operation (DESIGN §4 has the stamps
+// and the same-box A/B of each step).
+#include <atomic>
 #include "common.h"
 #include "pe_sin.h"
 #include "stream16.h"
 
 namespace nerf {
+
+// Diagnostic build (scripts/microbench/mlp16s_stamps.hip, never the library): per-wave s_memtime stamps,
+// kept in LDS words of the wave's own (LDS writes leave the stream's counted vmcnt alone) and copied to
+// a buffer of their own after the wave's last store.  Stamps: 0 entry | 1 first MFMA | 2 + L end of
+// trunk layer L (0..7) | 10 end of the colour layer | 11 last store; 12, 13: s_memrealtime at 0 and 11.
+#ifdef NERF_MLP16S_STAMPS
+__device__ unsigned long long nerf16s_stamps[65536][16];
+constexpr int kSStampFloats = kW16Waves * 32;
+constexpr int kSStampIter = 8;   // the block (of the workgroup's) that is stamped
+#define STAMP16S_ASM(i, insn)                                                               \
+  do {                                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                      \
+    unsigned long long t_;                                                                  \
+    asm volatile(insn " %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                 \
+    __builtin_amdgcn_sched_barrier(0);                                                      \
+    if (lane == 0 && stamp_on) reinterpret_cast<unsigned long long*>(lds + kSLdsFloats)[wave * 16 + (i)] = t_; \
+  } while (0)
+#define STAMP16S(i) STAMP16S_ASM(i, "s_memtime")
+#define STAMP16S_REAL(i) STAMP16S_ASM(i, "s_memrealtime")
+#else
+constexpr int kSStampFloats = 0;
+#define STAMP16S(i) do {} while (0)
+#define STAMP16S_REAL(i) do {} while (0)
+#endif
 
 __device__ __forceinline__ f32x4 mfma16s(h16x8 a, h16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
@@ -58,6 +92,7 @@ constexpr int kSLdsRgbFloats = 3 * kDirHidden + 4;
 constexpr int kSLdsFeat = kSLdsRgb + kSLdsRgbFloats;
 constexpr int kSLdsFloats = kSLdsFeat + kW16Waves * kRayFeat;
 static_assert(kSLdsRgb % 4 == 0 && kSLdsFeat % 4 == 0, "LDS vector layout");
+static_assert((kS16Chunks & (kS16Chunks - 1)) == 0 && kS16Chunks % 4 == 0, "the stream wraps onto the same ring slots");
 
 typedef h16x8 STile[2][2];   // a tile's fragments: [row half][hi, lo]
 typedef f32x4 SAcc[8][2][2]; // [tile][row half][sample tile]
@@ -115,7 +150,7 @@ __device__ __forceinline__ void ssegment(const STile& a, const Operand& b0, cons
 }
 
 // Side-work schedules, by (chunk i of the group, segment): which quarter (or PE operand) runs there.
-enum SSide { kSNone, kSPrev, kSCur, kSL0, kSSkipPrev, kSSkipCur };
+enum SSide { kSNone, kSPrev, kSCur, kSL0, kSSkipPrev, kSSkipCur, kSPrevPe, kSCurPe };
 // The skip layer's PE operands (k-steps 8, 9; two sample tiles each) are split from the wave's LDS
 // copy just before each group reads them: k-step 8's in chunk 7 (segments 0, 2), 9's in chunk 8
 // (segments 0, 2), so they hold registers only while read (the rest of the layer needs all of in[]).
@@ -141,8 +176,20 @@ __device__ __forceinline__ constexpr int sq_cur(int i, int seg) {
   if (cnt[i] == 3) return seg >= 1 ? base[i] + seg - 1 : -1;
   return seg == 1 ? base[i] : (seg == 3 ? base[i] + 1 : -1);
 }
+// The next block's positional encoding (32 values per lane) runs one value per segment in the 32
+// segments of layer 7's group B and of the colour layer (8 chunks each) that carry no quarter: value
+// 0..15 in group B's free segments in order, 16..31 in the colour layer's.
+template <bool CUR>
+__device__ __forceinline__ constexpr int spe_next(int i, int seg) {
+  if (i >= 8 || (CUR ? sq_cur(i, seg) : sq_prev(i, seg)) >= 0) return -1;
+  int n = 0;
+  for (int k = 0; k < 4 * i + seg; ++k) n += (CUR ? sq_cur(k / 4, k % 4) : sq_prev(k / 4, k % 4)) < 0;
+  return n + (CUR ? 0 : 16);
+}
+static_assert(spe_next<true>(7, 2) == 15 && spe_next<false>(7, 3) == 31, "32 free segments");
 template <int KIND>
 __device__ __forceinline__ constexpr int side_count(int i, int seg) {
+  if constexpr (KIND == kSPrevPe || KIND == kSCurPe) return 1;
   if constexpr (KIND == kSPrev) return sq_prev(i, seg) >= 0;
   if constexpr (KIND == kSSkipPrev) return (sq_prev(i, seg) >= 0) + (spe_at(i, seg) >= 0);
   if constexpr (KIND == kSCur) return sq_cur(i, seg) >= 0;
@@ -159,10 +206,18 @@ __device__ __forceinline__ constexpr int svpg(int i, int seg) {
 // One chunk-step: chunk c (global index, ring slot SLOT) = k-step i of group G; b0 / b1 its sample
 // tiles' operands.  On entry chunk c is published and tiles 0-2 of its fragments are in a[0..2].
 // TAIL = chunks left after c (capped at 3).
-template <int G, int SLOT, bool FIRST, int TAIL, int KIND, int I, typename Side>
+// WRAP (the colour layer in the block loop): the chunk three ahead is taken modulo the 128-chunk
+// stream, a multiple of the 4-slot ring, so the next block's chunks keep their slots.
+// pub(I) runs right behind the publish: the only pieces in flight there are chunk c+2's, a chunk-step
+// old, so a compiler-counted wait for loads of the kernel's own costs next to nothing there.
+struct SNoPub {
+  template <typename I>
+  __device__ __forceinline__ void operator()(I) const {}
+};
+template <int G, int SLOT, bool FIRST, int TAIL, int KIND, int I, bool WRAP, typename Side, typename Pub>
 __device__ __forceinline__ void schunk(const float* __restrict__ stream, int c, float* lds, uint32_t lds_dma,
                                        uint32_t voff, const uint32_t (&off)[2], STile (&a)[4], const Operand& b0,
-                                       const Operand& b1, SAcc& acc, Side&& side) {
+                                       const Operand& b1, SAcc& acc, Side&& side, Pub&& pub) {
   const float* cur = lds + SLOT * kChunkFloats;
   const float* nxt = lds + ((SLOT + 1) & 3) * kChunkFloats;
   auto none = [](auto) {};
@@ -182,10 +237,13 @@ __device__ __forceinline__ void schunk(const float* __restrict__ stream, int c, 
     wait_vmcnt<TAIL >= 2 ? 4 : 0>();
     __builtin_amdgcn_s_barrier();
   }
+  pub(std::integral_constant<int, I>{});
   // DMA of chunk c+3 into the slot chunk c-1 used (every wave's reads of it fed MFMAs issued before
   // the barrier): pieces 0, 1 in segment 1, 2 and 3 in segments 2, 3, after a chain's MFMAs
   auto dma = [&](auto pc) __attribute__((always_inline)) {
-    if constexpr (TAIL >= 3) chunk_dma_piece<(SLOT + 3) & 3, decltype(pc)::value>(stream, c + 3, lds_dma, voff);
+    if constexpr (TAIL >= 3)
+      chunk_dma_piece<(SLOT + 3) & 3, decltype(pc)::value>(stream, WRAP ? (c + 3) & (kS16Chunks - 1) : c + 3, lds_dma,
+                                                           voff);
   };
   ssegment<G, 1, FIRST, (TAIL >= 1), svpg<KIND>(I, 1)>(a[1], b0, b1, acc, [&]() __attribute__((always_inline)) {
     if constexpr (TAIL >= 1) sread_tile<0>(nxt, off, a[0]);
@@ -207,16 +265,17 @@ __device__ __forceinline__ void schunk(const float* __restrict__ stream, int c, 
 
 // A group of NSTEP chunk-steps from global chunk c0 (ring slot SLOT0); operand(i, st) gives k-step
 // i's B operand of sample tile st.  TAIL_END = chunks after this group (capped at 3).
-template <int G, int NSTEP, int SLOT0, int TAIL_END, int KIND, typename Opnd, typename Side>
+template <int G, int NSTEP, int SLOT0, int TAIL_END, int KIND, bool WRAP = false, typename Opnd, typename Side,
+          typename Pub = SNoPub>
 __device__ __forceinline__ void sgroup(const float* __restrict__ stream, int c0, float* lds, uint32_t lds_dma,
                                        uint32_t voff, const uint32_t (&off)[2], STile (&a)[4], SAcc& acc,
-                                       Opnd&& operand, Side&& side) {
+                                       Opnd&& operand, Side&& side, Pub&& pub = Pub{}) {
   static_for<NSTEP>([&](auto ic) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
     constexpr int left = NSTEP - 1 - i + TAIL_END;
-    schunk<G, (SLOT0 + i) & 3, i == 0, (left < 3 ? left : 3), KIND, i>(
+    schunk<G, (SLOT0 + i) & 3, i == 0, (left < 3 ? left : 3), KIND, i, WRAP>(
         stream, c0 + i, lds, lds_dma, voff, off, a, operand(ic, std::integral_constant<int, 0>{}),
-        operand(ic, std::integral_constant<int, 1>{}), acc, side);
+        operand(ic, std::integral_constant<int, 1>{}), acc, side, pub);
   });
 }
 
@@ -289,27 +348,50 @@ __global__ void __launch_bounds__(64 * kW16Waves, 1)
 mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, const float* __restrict__ dirs,
               const float* __restrict__ zv, int64_t M, int N, const float* __restrict__ feat,
               float* __restrict__ rgb, float* __restrict__ sigma, const int* __restrict__ out_slot, int out_T) {
-  __shared__ __attribute__((aligned(16))) float lds[kSLdsFloats];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, li = lane & 15;
-  const int64_t s0 = ((int64_t)blockIdx.x * kW16Waves + wave) * 32;
+  __shared__ __attribute__((aligned(16))) float lds[kSLdsFloats + kSStampFloats];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane0 = threadIdx.x & 63;
   // every wave runs to the end (the weight stream has barriers); tail lanes repeat sample M-1.  A
   // launch spans < 2^31 samples (capi.hip max_launch_samples): 32-bit sample and ray indices.
   const int mlast = (int)(M - 1);
-  auto sample_of = [&](int st) { return imin64(s0 + 16 * st + li, (int64_t)mlast); };
-  float x[2][3];
+  // The workgroup runs sample blocks blockIdx.x, blockIdx.x + gridDim.x, ...: the trip count depends
+  // on blockIdx.x alone, so the four waves run the same barriers.
+  const int nblk = (int)((M + 32 * kW16Waves - 1) / (32 * kW16Waves));
+  int blk = blockIdx.x;
+  auto sample_of = [&](int b, int st) {
+    return imin64(((int64_t)b * kW16Waves + wave) * 32 + 16 * st + (lane0 & 15), (int64_t)mlast);
+  };
+  // a block's inputs as loaded (SIn) and its sample positions from them
+  float in_z[2], in_o[2][3], in_d[2][3];
+  auto load_inputs = [&](int b) __attribute__((always_inline)) {
 #pragma unroll
-  for (int st = 0; st < 2; ++st) {
-    const int sm = (int)sample_of(st), ry = sm / N;
-    if (zv) {   // pts = o + d*z with separate roundings (ray_utils.py:86)
-      const float z = zv[sm];
+    for (int st = 0; st < 2; ++st) {
+      const int sm = (int)sample_of(b, st);
+      const int64_t row = zv ? sm / N : sm;   // the sample's ray, or the point itself
 #pragma unroll
-      for (int c = 0; c < 3; ++c) x[st][c] = orig[3 * ry + c] + dirs[3 * ry + c] * z;
-    } else {
+      for (int c = 0; c < 3; ++c) in_o[st][c] = orig[3 * row + c];
+      in_z[st] = 0.0f;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) x[st][c] = orig[3 * sm + c];
+      for (int c = 0; c < 3; ++c) in_d[st][c] = 0.0f;
+      if (zv) {
+        in_z[st] = zv[sm];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) in_d[st][c] = dirs[3 * row + c];
+      }
     }
-  }
+  };
+  float x[2][3];
+  auto positions = [&](float (&x)[2][3]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {   // pts = o + d*z with separate roundings (ray_utils.py:86)
+        const float p = in_o[st][c] + in_d[st][c] * in_z[st];
+        x[st][c] = zv ? p : in_o[st][c];
+      }
+  };
+  load_inputs(blk);
+  positions(x);
+  // once per workgroup: biases, density head, layer constants and the rgb head into LDS
   for (int i = threadIdx.x; i < kSLdsVecFloats / 4; i += 64 * kW16Waves)
     reinterpret_cast<f32x4*>(lds + kSLdsBias)[i] = reinterpret_cast<const f32x4*>(packed + kOffBias)[i];
   if (threadIdx.x < kS16Consts) lds[kSLdsConsts + threadIdx.x] = packed[kOffScale16 + threadIdx.x];
@@ -318,87 +400,173 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_sched_barrier(0);
   const float* stream = packed + kOff16;
-  const uint32_t lds_dma = (uint32_t)(uintptr_t)(lptr_t)lds + 1024u * wave;
+  uint32_t lds_dma = (uint32_t)(uintptr_t)(lptr_t)lds + 1024u * wave;
+  // fragment offsets: row half r, lane l reads piece (g >> 1) lane R_r(l & 15) + 32 (g & 1)
+  auto fragment_offsets = [](int l, uint32_t (&off)[2]) __attribute__((always_inline)) {
+    const int li = l & 15, hh = (l >> 4) & 1, ss = l >> 5;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) off[r] = (uint32_t)(ss * 2048 + 4 * ((li & 7) + 8 * r + 16 * (li >> 3) + 32 * hh));
+  };
+  float* pe_mine = lds + kSLdsPe + wave * kPeSteps * 64;
+  const float* bias = lds + kSLdsBias;
+  const float* ws = lds + kSLdsSigmaW;
+  const float* cst = lds + kSLdsConsts;
+  const bool one_ray = (N & 31) == 0;
+  float* feat_mine = lds + kSLdsFeat + wave * kRayFeat;
+  // the first block's chunks 0-2 and its chunk 0's tiles 0-2 (chunks 1-2 in flight); later blocks get
+  // theirs from the colour layer of the block before
+  STile a[4];
+  {
+    const uint32_t voff = 16u * lane0 + 1024u * wave;
+    chunk_dma<0>(stream, 0, lds_dma, voff);
+    chunk_dma<1>(stream, 1, lds_dma, voff);
+    chunk_dma<2>(stream, 2, lds_dma, voff);
+    uint32_t off[2];
+    fragment_offsets(lane0, off);
+    wait_vmcnt<8>();
+    __builtin_amdgcn_s_barrier();
+    sread_tile<0>(lds, off, a[0]);
+    sread_tile<1>(lds, off, a[1]);
+    sread_tile<2>(lds, off, a[2]);
+  }
+
+  Operand pe_op[4];   // layer 0's (and, re-split, the skip layer's) PE operands: [t][st] -> 2 t + st
+  bool full = true;   // this block's encoding is still to be computed
+#ifdef NERF_MLP16S_STAMPS
+  int it = 0;
+#endif
+#pragma unroll 1
+  for (;;) {
+  // The stream's base, the ring's LDS address and the lane are opaque to the compiler per block:
+  // otherwise it hoists every chunk's piece addresses and every per-lane LDS address and PE constant
+  // (loop-invariant, over a hundred registers) out of the block loop and spills.  What derives from
+  // the lane (a dozen VALU instructions) is therefore computed per block.
+  asm volatile("" : "+s"(stream));
+  asm volatile("" : "+s"(lds_dma));
+  int lane = lane0;
+  asm volatile("" : "+v"(lane));
+  const int g = lane >> 4, li = lane & 15, hh = g & 1, ss = g >> 1;
   const uint32_t voff = 16u * lane + 1024u * wave;
-  chunk_dma<0>(stream, 0, lds_dma, voff);
-  chunk_dma<1>(stream, 1, lds_dma, voff);
-  chunk_dma<2>(stream, 2, lds_dma, voff);
+  uint32_t off[2];
+  fragment_offsets(lane, off);
+  const int nlane = 4 * hh + 16 * ss;   // this lane's neuron offset in a 16 x 16 output tile (+ 8r + e)
+#ifdef NERF_MLP16S_STAMPS
+  const bool stamp_on = it == kSStampIter || (it < kSStampIter && blk + (int)gridDim.x >= nblk);
+  ++it;
+#endif
+  STAMP16S(0);
+  STAMP16S_REAL(12);
+  const int64_t s0 = ((int64_t)blk * kW16Waves + wave) * 32;
 
   // PE: lane group g = 2s + h computes slots 8 (2t + s) + j (t = 0, 1) of both its samples, sin for
   // h = 0 and cos for h = 1 (pe_feature; slot 30: x0 | x1, 31: x2 | 0).  Slot p < 30 is frequency
   // p / 3 of coordinate p % 3.  A wave with a coordinate beyond pe_sin.h's range takes sincosf.
-  const int hh = g & 1, ss = g >> 1;
-  float pe[2][2][8];
-  float ax = 0.0f;
-#pragma unroll
-  for (int st = 0; st < 2; ++st) ax = fmaxf(ax, fmaxf(fabsf(x[st][0]), fmaxf(fabsf(x[st][1]), fabsf(x[st][2]))));
-  auto pe_arg = [&](int st, int p) __attribute__((always_inline)) {
+  // The block before computed this block's encoding and layer-0 operands in its MFMA shadow (side_pe_next
+  // below); only the workgroup's first block and a wave with such a coordinate (`full`) do it here.
+  auto pe_arg = [&](const float (&xa)[2][3], int st, int p) __attribute__((always_inline)) {
     const int fi = p / 3, fc = p - 3 * fi;
-    const float xc = fc == 0 ? x[st][0] : (fc == 1 ? x[st][1] : x[st][2]);
+    const float xc = fc == 0 ? xa[st][0] : (fc == 1 ? xa[st][1] : xa[st][2]);
     return xc * __int_as_float((127 + (fi < kPosLevels ? fi : 0)) << 23);   // x 2^fi, exact
   };
-  auto pe_tail = [&](int st, int p, float v) __attribute__((always_inline)) {
-    return p < 3 * kPosLevels ? v : (p == 30 ? (hh ? x[st][1] : x[st][0]) : (hh ? 0.0f : x[st][2]));
+  auto pe_tail = [&](const float (&xa)[2][3], int st, int p, float v) __attribute__((always_inline)) {
+    return p < 3 * kPosLevels ? v : (p == 30 ? (hh ? xa[st][1] : xa[st][0]) : (hh ? 0.0f : xa[st][2]));
   };
-  if (__any(ax * (float)(1 << (kPosLevels - 1)) > kPeSinMax)) {
+  auto pe_beyond = [&](const float (&xa)[2][3]) __attribute__((always_inline)) {
+    float ax = 0.0f;
 #pragma unroll
     for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int p = 8 * (2 * t + ss) + j;
-          float sn, cs;
-          sincosf(pe_arg(st, p), &sn, &cs);
-          pe[st][t][j] = pe_tail(st, p, hh ? cs : sn);
-        }
-  } else {
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int p = 8 * (2 * t + ss) + j;
-          pe[st][t][j] = pe_tail(st, p, pe_sin_reduced(pe_arg(st, p), hh));
-        }
-  }
-  float* pe_mine = lds + kSLdsPe + wave * kPeSteps * 64;
-#pragma unroll
-  for (int st = 0; st < 2; ++st)
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pe_mine[((st * 2 + t) * 8 + j) * 64 + lane] = pe[st][t][j];
+      ax = fmaxf(ax, fmaxf(fabsf(xa[st][0]), fmaxf(fabsf(xa[st][1]), fabsf(xa[st][2]))));
+    return __any(ax * (float)(1 << (kPosLevels - 1)) > kPeSinMax) != 0;
+  };
+  auto pe_bound = [&](const float (&xa)[2][3], int st) __attribute__((always_inline)) {
+    return fmaxf(1.0f, fmaxf(fabsf(xa[st][0]), fmaxf(fabsf(xa[st][1]), fabsf(xa[st][2]))));
+  };
   float m_pe[2];
-#pragma unroll
-  for (int st = 0; st < 2; ++st) m_pe[st] = fmaxf(1.0f, fmaxf(fabsf(x[st][0]), fmaxf(fabsf(x[st][1]), fabsf(x[st][2]))));
-
-  const float* bias = lds + kSLdsBias;
-  const float* ws = lds + kSLdsSigmaW;
-  const float* cst = lds + kSLdsConsts;
   float s_cur[2], inv_cur[2], s_nxt[2], inv_prev[2], m[2] = {0.0f, 0.0f}, part[2] = {0.0f, 0.0f};
-  Operand pe_op[4];   // [t][st] -> 2 t + st
 #pragma unroll
   for (int st = 0; st < 2; ++st) {
+    m_pe[st] = pe_bound(x, st);
     s_cur[st] = pow2_scale(m_pe[st]);
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) split_into(pe[st][t][j] * s_cur[st], pe_op[2 * t + st], j);
   }
-  // fragment offsets: row half r, lane l reads piece (g >> 1) lane R_r(l & 15) + 32 (g & 1)
-  uint32_t off[2];
+  if (full) {
+    float pe[2][2][8];
+    if (pe_beyond(x)) {
 #pragma unroll
-  for (int r = 0; r < 2; ++r) off[r] = (uint32_t)(ss * 2048 + 4 * ((li & 7) + 8 * r + 16 * (li >> 3) + 32 * hh));
-  const int nlane = 4 * hh + 16 * ss;   // this lane's neuron offset in a 16 x 16 output tile (+ 8r + e)
-
-  wait_vmcnt<8>();                                          // this wave's part of chunk 0 (chunks 1-2 in flight)
-  __builtin_amdgcn_s_barrier();
-  STile a[4];
-  sread_tile<0>(lds, off, a[0]);
-  sread_tile<1>(lds, off, a[1]);
-  sread_tile<2>(lds, off, a[2]);
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int p = 8 * (2 * t + ss) + j;
+            float sn, cs;
+            sincosf(pe_arg(x, st, p), &sn, &cs);
+            pe[st][t][j] = pe_tail(x, st, p, hh ? cs : sn);
+          }
+    } else {
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int p = 8 * (2 * t + ss) + j;
+            pe[st][t][j] = pe_tail(x, st, p, pe_sin_reduced(pe_arg(x, st, p), hh));
+          }
+    }
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          pe_mine[((st * 2 + t) * 8 + j) * 64 + lane] = pe[st][t][j];
+          split_into(pe[st][t][j] * s_cur[st], pe_op[2 * t + st], j);
+        }
+  }
+  // the next block (one past the end repeats sample M-1): its inputs are loaded behind a publish of
+  // layer 7's group A, and its encoding runs in the segments of layer 7's group B and of the colour
+  // layer that carry no quarter, one value each, written to the wave's LDS copy (dead since layer 4)
+  // and split into pe_op at the next block's layer-0 scale
+  const int nxt_blk = blk + (int)gridDim.x;
+  float xn[2][3], s_n[2];
+  bool beyond_n = false;
+  Operand pe_nx[4];   // (its own registers: pe_op's hold the skip layer's re-split until layer 4 ends)
+  // (the lane once more opaque: otherwise every slot's frequency and coordinate select, shared with
+  // the code above, stays in registers from there to here)
+  int lane_n = lane;
+  auto pub_next = [&](auto ic) __attribute__((always_inline)) {
+    if constexpr (decltype(ic)::value == 0) load_inputs(nxt_blk);
+    if constexpr (decltype(ic)::value == 2) {
+      asm volatile("" : "+v"(lane_n));
+      positions(xn);
+#pragma unroll
+      for (int st = 0; st < 2; ++st) s_n[st] = pow2_scale(pe_bound(xn, st));
+      beyond_n = pe_beyond(xn);
+    }
+  };
+  auto side_pe_next = [&](auto nc, auto ph) __attribute__((always_inline)) {
+    constexpr int n = decltype(nc)::value;
+    if constexpr (n >= 0 && decltype(ph)::value == 1) {
+      constexpr int st = n >> 4, t = (n >> 3) & 1, j = n & 7;
+      // the lane's slot is 16 t + j (lane groups 0, 1) or 16 t + 8 + j (groups 2, 3): both slots'
+      // frequency and coordinate are compile-time, one select picks the lane's (no branch, and the
+      // same exact product x 2^f as pe_arg)
+      constexpr int p0 = 16 * t + j, p1 = p0 + 8;
+      constexpr int f0 = p0 / 3, c0 = p0 % 3, f1 = p1 / 3 < kPosLevels ? p1 / 3 : 0, c1 = p1 % 3;
+      const bool upper = lane_n >= 32;
+      const int hn = (lane_n >> 4) & 1;
+      const float a0 = xn[st][c0] * (float)(1 << f0), a1 = xn[st][c1] * (float)(1 << f1);
+      const float r = pe_sin_reduced(upper ? a1 : a0, hn);
+      float v = r;
+      if constexpr (p1 == 30) v = upper ? (hn ? xn[st][1] : xn[st][0]) : r;
+      if constexpr (p1 == 31) v = upper ? (hn ? 0.0f : xn[st][2]) : r;
+      pe_mine[((st * 2 + t) * 8 + j) * 64 + lane_n] = v;
+      split_into(v * s_n[st], pe_nx[2 * t + st], j);
+      // (the operand materialised here: otherwise the compiler keeps v to convert it in a pair with
+      // the next segment's value)
+      asm volatile("" : "+v"(pe_nx[2 * t + st].hi), "+v"(pe_nx[2 * t + st].lo));
+    }
+  };
   SAcc acc;
   Operand in[16];
 #pragma unroll
@@ -412,6 +580,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
     return pe_op[2 * decltype(i)::value + decltype(st)::value];
   };
 
+  STAMP16S(1);
   // ---- layer 0: PE (2 k-steps of 32) -> 256; group B converts group A's tiles 0-3 into in[0..7],
   // two quarters per segment
   sgroup<0, 2, 0, 3, kSNone>(stream, 0, lds, lds_dma, voff, off, a, acc, pe_operand_of,
@@ -425,6 +594,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
                                                                              m, part, qv[1]);
                            });
 
+  STAMP16S(2);
   // ---- layers 1..7 (mlp16's schedule; on entry in[0..7] hold y_{L-1} tiles 0-3 at s_cur, its tiles
   // 4-7 wait in acc[4..7], m the sample tiles' maxima of y_{L-1} tiles 0-3)
 #pragma unroll
@@ -463,7 +633,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   // density head).  Layers 1-3 and 5-6 run as loops of the plain body, layers 4 and 7 on their own:
   // one body with the skip and sigma variants behind runtime branches spilled (the register
   // allocator then has to serve every variant's live ranges at the loop's back edge).
-  auto layer = [&](int L, auto skip_tag, auto sg_tag) __attribute__((always_inline)) {
+  auto layer = [&](int L, auto skip_tag, auto sg_tag, auto&& pub_a) __attribute__((always_inline)) {
     constexpr bool SKIP = decltype(skip_tag)::value;
     constexpr bool SG = decltype(sg_tag)::value;
 #pragma unroll
@@ -484,7 +654,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
       sgroup<0, 8, 0, 3, kSPrev>(stream, c0, lds, lds_dma, voff, off, a, acc, act_operand,
                                  [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
                                    side_prev(i, seg, ph, NoSigma{});
-                                 });
+                                 }, pub_a);
     }
     // the inputs of layer L are known: the scale of layer L+1's inputs from the bound on y_L
 #pragma unroll
@@ -502,10 +672,14 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
                                        side_pe(i, seg, ph);
                                      });
     } else {
-      sgroup<1, 8, 0, 3, kSCur>(stream, c0 + 8, lds, lds_dma, voff, off, a, acc, act_operand,
-                                [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
-                                  side_cur(i, seg, ph, bias_l, sg_tag);
-                                });
+      // (layer 7, SG: the next block's encoding in the free segments)
+      sgroup<1, 8, 0, 3, SG ? kSCurPe : kSCur>(
+          stream, c0 + 8, lds, lds_dma, voff, off, a, acc, act_operand,
+          [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
+            side_cur(i, seg, ph, bias_l, sg_tag);
+            if constexpr (SG)
+              side_pe_next(std::integral_constant<int, spe_next<true>(decltype(i)::value, decltype(seg)::value)>{}, ph);
+          });
     }
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
@@ -513,19 +687,21 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
       s_cur[st] = s_nxt[st];
     }
     bias_prev = bias_l;
+    STAMP16S(2 + L);
   };
 #pragma unroll 1
-  for (int L = 1; L < kSkipLayer; ++L) layer(L, NoSigma{}, NoSigma{});
-  layer(kSkipLayer, Sigma{}, NoSigma{});
+  for (int L = 1; L < kSkipLayer; ++L) layer(L, NoSigma{}, NoSigma{}, SNoPub{});
+  layer(kSkipLayer, Sigma{}, NoSigma{}, SNoPub{});
 #pragma unroll 1
-  for (int L = kSkipLayer + 1; L < 7; ++L) layer(L, NoSigma{}, NoSigma{});
-  layer(7, NoSigma{}, Sigma{});
+  for (int L = kSkipLayer + 1; L < 7; ++L) layer(L, NoSigma{}, NoSigma{}, SNoPub{});
+  layer(7, NoSigma{}, Sigma{}, pub_next);
 
   // ---- colour layer: h7 -> 128 (one group of 8 chunks); its side converts y_7 tiles 4-7 and
-  // finishes the density head.  When N is a multiple of 32 the wave's samples lie on one ray: its
-  // 1 KiB of ray features is DMA'd into LDS meanwhile (the stream's last vmcnt(0) covers it).
-  const bool one_ray = (N & 31) == 0;
-  float* feat_mine = lds + kSLdsFeat + wave * kRayFeat;
+  // finishes the density head.  The stream wraps: the layer's chunk-steps DMA the next block's chunks
+  // 0-2, publish chunk 0 and read its tiles 0-2, which is where layer 0 starts (after the workgroup's
+  // last block those chunks are fetched for nothing, once per workgroup).  When N is a multiple of 32
+  // the wave's samples lie on one ray: its 1 KiB of ray features is DMA'd into LDS meanwhile; it is
+  // older than the wrapped chunks' pieces, so the layer's publishes cover it.
   if (one_ray) {
     const char* src = reinterpret_cast<const char*>(feat + (imin64(s0, M - 1) / N) * kRayFeat);
     const uint32_t dst = (uint32_t)(uintptr_t)(lptr_t)feat_mine;
@@ -542,11 +718,14 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   }
 #pragma unroll
   for (int st = 0; st < 2; ++st) inv_cur[st] = cst[kS16InvW + 8] / s_cur[st];
-  sgroup<0, 8, 0, 0, kSPrev>(stream, s16_chunk0(8), lds, lds_dma, voff, off, a, acc, act_operand,
-                             [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
-                               side_prev(i, seg, ph, Sigma{});
-                             });
+  sgroup<0, 8, 0, 3, kSPrevPe, true>(
+      stream, s16_chunk0(8), lds, lds_dma, voff, off, a, acc, act_operand,
+      [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
+        side_prev(i, seg, ph, Sigma{});
+        side_pe_next(std::integral_constant<int, spe_next<false>(decltype(i)::value, decltype(seg)::value)>{}, ph);
+      });
 
+  STAMP16S(10);
   // density head: sigma = ReLU(density_head(ReLU(h7))) (models.py:137-138), f32
   float sig[2];
 #pragma unroll
@@ -573,22 +752,24 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
         }
       }
   };
+  if (one_ray) wait_vmcnt<8>();   // the feature piece (younger: the next block's chunks 1-2)
   if (one_ray) {
-    wait_vmcnt<0>();
     colour_head(feat_mine, 0);
     colour_head(feat_mine, 1);
   } else {
-    colour_head(feat + (int64_t)((int)sample_of(0) / N) * kRayFeat, 0);
-    colour_head(feat + (int64_t)((int)sample_of(1) / N) * kRayFeat, 1);
+    colour_head(feat + (int64_t)((int)sample_of(blk, 0) / N) * kRayFeat, 0);
+    colour_head(feat + (int64_t)((int)sample_of(blk, 1) / N) * kRayFeat, 1);
   }
-  float out[2][3];
+  // Lane group st (0, 1) writes sample tile st.  Every lane holds both tiles' sums, but evaluates the
+  // sigmoid, a double-precision exp, only for the tile its group writes (groups 2, 3 mirror 0, 1):
+  // +0.5 % frame rate on the one-block kernel, same box (profiles/r07/ab_render_stage2_heads_gap.log).
+  float out[3];
 #pragma unroll
-  for (int st = 0; st < 2; ++st)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = ssum4(pr[st][c]) + wr[3 * kDirHidden + c];
-      out[st][c] = 1.0f / (1.0f + expf_rn(-v));                        // sigmoid (models.py:159-160)
-    }
+  for (int c = 0; c < 3; ++c) {
+    const float v0 = ssum4(pr[0][c]) + wr[3 * kDirHidden + c], v1 = ssum4(pr[1][c]) + wr[3 * kDirHidden + c];
+    const float v = (g & 1) ? v1 : v0;
+    out[c] = 1.0f / (1.0f + expf_rn(-v));                              // sigmoid (models.py:159-160)
+  }
   // lane group st writes sample tile st
   if (g < 2) {
     const int st = g;
@@ -597,9 +778,41 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
       const int64_t o_s = out_slot ? (int64_t)(sm / N) * out_T + out_slot[sm] : (int64_t)sm;
       sigma[o_s] = st ? sig[1] : sig[0];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) rgb[3 * o_s + c] = st ? out[1][c] : out[0][c];
+      for (int c = 0; c < 3; ++c) rgb[3 * o_s + c] = out[c];
     }
   }
+  STAMP16S(11);
+  STAMP16S_REAL(13);
+  if (nxt_blk >= nblk) break;
+  blk = nxt_blk;
+  full = beyond_n;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) pe_op[k] = pe_nx[k];
+#pragma unroll
+  for (int st = 0; st < 2; ++st)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[st][c] = xn[st][c];
+  }
+  wait_vmcnt<0>();   // the wrapped stream's chunks 0-2 after the last block: nothing outstanding at the end
+#ifdef NERF_MLP16S_STAMPS
+  if (const int64_t w_ = (int64_t)blockIdx.x * kW16Waves + wave; w_ < 65536 && lane0 == 0)
+    for (int i = 0; i < 16; ++i)
+      nerf16s_stamps[w_][i] = reinterpret_cast<const unsigned long long*>(lds + kSLdsFloats)[wave * 16 + i];
+#endif
+}
+
+// Workgroups of the persistent grid: one per CU of the current device (the kernel's registers and its
+// 111 KiB of LDS leave room for one workgroup per CU).  Read once per device.
+static int device_cus() {
+  static std::atomic<int> cached[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  int n = cached[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+    cached[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
 }
 
 int launch_mlp16s(const float* packed, const float* o, const float* d, const float* z, int64_t R, int N,
@@ -608,7 +821,9 @@ int launch_mlp16s(const float* packed, const float* o, const float* d, const flo
   if (M == 0) return NERF_OK;
   constexpr int per_block = 32 * kW16Waves;
   const int64_t blocks = (M + per_block - 1) / per_block;
-  hipLaunchKernelGGL(mlp16s_kernel, dim3((unsigned)blocks), dim3(64 * kW16Waves), 0, s, packed, o, d, z, M, N, feat,
+  const int cus = device_cus();
+  if (cus <= 0) return set_error(NERF_ERR_HIP, "mlp16s_kernel: cannot read the device's CU count");
+  hipLaunchKernelGGL(mlp16s_kernel, dim3((unsigned)(blocks < cus ? blocks : cus)), dim3(64 * kW16Waves), 0, s, packed, o, d, z, M, N, feat,
                      rgb, sigma, out_slot, out_T);
   return check_launch("mlp16s_kernel");
 }
