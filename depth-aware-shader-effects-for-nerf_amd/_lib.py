@@ -87,6 +87,21 @@ _SIGNATURES = {
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                         ctypes.c_void_p]),
+    # occupancy-grid sample skipping (include/nerfmi.h)
+    "nerf_occupancy_words": (ctypes.c_size_t, [ctypes.c_int]),
+    "nerf_occupancy_pack": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, ctypes.c_float, _V, _V]),
+    "nerf_occupancy_dilate": (ctypes.c_int, [_V, ctypes.c_int, _V, _V]),
+    "nerf_occupancy_classify_workspace_bytes": (ctypes.c_size_t, [_I64, ctypes.c_int]),
+    "nerf_occupancy_classify": (ctypes.c_int, [_V, _V, _V, _I64, ctypes.c_int, _V, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _V, _V,
+                                               _V, _V, ctypes.c_size_t, _V]),
+    "nerf_mlp_forward_live": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V, _V, _V, _V]),
+    "nerf_render_occ_workspace_bytes": (ctypes.c_size_t, [_I64, ctypes.c_int, ctypes.c_int]),
+    "nerf_render_rays_occ": (ctypes.c_int, [_V, _V, _V, _I64, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                            ctypes.c_int, _V, _V, ctypes.c_int, _V, _V, ctypes.c_uint64, _I64, _V,
+                                            _I64, _V, ctypes.c_int, ctypes.POINTER(ctypes.c_float),
+                                            ctypes.POINTER(ctypes.c_float), _V, _V, _V, _V, _V, _V, _V,
+                                            ctypes.c_size_t, _V]),
     # training (include/nerfmi_train.h)
     "nerf_packed_transposed_floats": (ctypes.c_size_t, []),
     "nerf_pack_weights_transposed": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,

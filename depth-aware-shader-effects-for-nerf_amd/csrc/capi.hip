@@ -604,4 +604,209 @@ static int render_rays_chunk(const float* packed, const float* rays_o, const flo
                                  weights_out, s);
 }
 
+// --------------------------------------------------------------- occupancy-grid sample skipping
+// (include/nerfmi.h; kernels in occupancy.hip and mlp16s.hip's gathered entry)
+#define REQUIRE_GRID(fn, G)                                                                               \
+  do {                                                                                                    \
+    if ((G) < 1 || (G) > 1024) return set_error(NERF_ERR_UNSUPPORTED, fn ": G=%d outside 1..1024", (G)); \
+  } while (0)
+
+size_t nerf_occupancy_words(int G) {
+  if (G < 1 || G > 1024) return 0;
+  return (size_t)(((int64_t)G * G * G + 31) / 32);
+}
+
+int nerf_occupancy_pack(const float* sigma_lattice, int G, int s, float threshold, uint32_t* bits,
+                        nerf_stream_t stream) {
+  REQUIRE(sigma_lattice && bits, "nerf_occupancy_pack: null pointer");
+  REQUIRE_GRID("nerf_occupancy_pack", G);
+  REQUIRE(s >= 1 && (int64_t)s * G <= 4096, "nerf_occupancy_pack: s=%d probes per cell with G=%d (s G <= 4096)", s, G);
+  return launch_occ_pack(sigma_lattice, G, s, threshold, bits, (hipStream_t)stream);
+}
+
+int nerf_occupancy_dilate(const uint32_t* bits_in, int G, uint32_t* bits_out, nerf_stream_t stream) {
+  REQUIRE(bits_in && bits_out, "nerf_occupancy_dilate: null pointer");
+  REQUIRE(bits_in != bits_out, "nerf_occupancy_dilate: in place");
+  REQUIRE_GRID("nerf_occupancy_dilate", G);
+  return launch_occ_dilate(bits_in, G, bits_out, (hipStream_t)stream);
+}
+
+size_t nerf_occupancy_classify_workspace_bytes(int64_t B, int n) {
+  if (B < 0 || n < 1 || B * (int64_t)n > max_launch_samples()) return 0;
+  return align_up(occ_block_count_bytes(B * (int64_t)n));
+}
+
+int nerf_occupancy_classify(const float* rays_o, const float* dirs, const float* z, int64_t B, int n,
+                            const uint32_t* bits, int G, const float* lo, const float* inv, int32_t* live,
+                            int32_t* live_count, uint8_t* mask, void* workspace, size_t ws_bytes,
+                            nerf_stream_t stream) {
+  REQUIRE(B >= 0 && n >= 1, "nerf_occupancy_classify: B=%lld n=%d", (long long)B, n);
+  REQUIRE(bits && lo && inv && live_count, "nerf_occupancy_classify: null pointer");
+  REQUIRE(B == 0 || (rays_o && dirs && z && live && workspace), "nerf_occupancy_classify: null pointer");
+  REQUIRE_GRID("nerf_occupancy_classify", G);
+  if (B * (int64_t)n > max_launch_samples())
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_occupancy_classify: %lld samples exceed the launch limit %lld",
+                     (long long)(B * (int64_t)n), (long long)max_launch_samples());
+  const size_t need = nerf_occupancy_classify_workspace_bytes(B, n);
+  if (ws_bytes < need)
+    return set_error(NERF_ERR_WORKSPACE, "nerf_occupancy_classify: workspace %zu < %zu bytes", ws_bytes, need);
+  return launch_occ_classify(rays_o, dirs, z, B, n, bits, G, lo, inv, live, live_count, mask, nullptr, nullptr,
+                             (uint32_t*)workspace, (hipStream_t)stream);
+}
+
+// The gathered MLP behind the profiling hook, as profiled_mlp (the recorded sample count is the
+// launch's R N: the live count stays on the device).
+static int profiled_mlp_live(const float* packed, const float* origins, const float* dirs, const float* z, int64_t R,
+                             int N, const float* feat, float* rgb, float* sigma, const int* live, const int* live_count,
+                             hipStream_t s) {
+  const bool rec = g_prof.on && g_prof.n < (int)g_prof.samples.size();
+  if (rec && hipEventRecord(g_prof.ev[2 * g_prof.n], s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "nerf profile: hipEventRecord failed");
+  if (int rc = launch_mlp16s_live(packed, origins, dirs, z, R, N, feat, rgb, sigma, live, live_count, s)) return rc;
+  if (rec) {
+    if (hipEventRecord(g_prof.ev[2 * g_prof.n + 1], s) != hipSuccess)
+      return set_error(NERF_ERR_HIP, "nerf profile: hipEventRecord failed");
+    g_prof.samples[g_prof.n++] = R * (int64_t)N;
+  }
+  return NERF_OK;
+}
+
+int nerf_mlp_forward_live(const float* packed, const float* origins, const float* dirs, const float* z_vals,
+                          int64_t R, int N, const float* ray_feat, const int32_t* live, const int32_t* live_count,
+                          float* rgb, float* sigma, nerf_stream_t stream) {
+  REQUIRE(R >= 0 && N >= 1, "nerf_mlp_forward_live: R=%lld N=%d", (long long)R, N);
+  REQUIRE(live_count, "nerf_mlp_forward_live: null pointer");
+  REQUIRE(R == 0 || (packed && origins && dirs && z_vals && ray_feat && live && rgb && sigma),
+          "nerf_mlp_forward_live: null pointer");
+  if (g_mlp_arith != NERF_ARITH_F16X3)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_mlp_forward_live: the gathered kernel is f16x3 only");
+  if (R * (int64_t)N > max_launch_samples())   // (the list indexes one launch: no chunking)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_mlp_forward_live: %lld samples exceed the launch limit %lld",
+                     (long long)(R * (int64_t)N), (long long)max_launch_samples());
+  return profiled_mlp_live(packed, origins, dirs, z_vals, R, N, ray_feat, rgb, sigma, live, live_count,
+                           (hipStream_t)stream);
+}
+
+// Workspace of nerf_render_rays_occ: the plain carve, then (each 256-B aligned) the live list
+// (B max(N, Nf) int32), the count and the classify block counts.
+enum { WO_LIVE, WO_COUNT, WO_BLOCKS, WO_COUNT_REGIONS };
+static size_t carve_occ(int64_t B, int N, int Nf, size_t* off, size_t* off_occ) {
+  size_t at = carve(B, N, Nf, off);
+  const int64_t per = B * (int64_t)(N > Nf ? N : Nf);
+  const size_t sizes[WO_COUNT_REGIONS] = {(size_t)per * 4, 4, occ_block_count_bytes(per)};
+  for (int i = 0; i < WO_COUNT_REGIONS; ++i) {
+    off_occ[i] = at;
+    at += align_up(sizes[i]);
+  }
+  return at;
+}
+
+size_t nerf_render_occ_workspace_bytes(int64_t B, int N, int Nf) {
+  if (B < 0 || N < 1 || Nf < 0) return 0;
+  const int64_t chunk = nerf_render_chunk_rays(N, Nf);
+  size_t off[W_COUNT], off_occ[WO_COUNT_REGIONS];
+  return carve_occ(B < chunk ? B : chunk, N, Nf, off, off_occ);
+}
+
+// render_rays_chunk's stage sequence with classify -> zero-fill -> gathered MLP in place of each MLP
+// launch.  Under NERF_ARITH_F32 every sample is evaluated by the f32 kernel and the classify pass
+// runs after it, zeroing the dead rows (the same result, no speed-up).
+static int render_rays_occ_chunk(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
+                                 double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
+                                 const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0,
+                                 const float* app, int64_t app_rows, const uint32_t* bits, int G, const float* lo,
+                                 const float* inv, float* rgb_map, float* depth_map, float* weights_out, float* z_out,
+                                 float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
+                                 hipStream_t s) {
+  if (B == 0) return NERF_OK;
+  REQUIRE(packed && rays_o && rays_d && t_vals && rgb_map && depth_map && workspace,
+          "nerf_render_rays_occ: null pointer");
+  REQUIRE(Nf == 0 || u_lin, "nerf_render_rays_occ: u_lin required when Nf > 0");
+  REQUIRE(app_rows == 0 || app, "nerf_render_rays_occ: null appearance");
+  size_t off[W_COUNT], off_occ[WO_COUNT_REGIONS];
+  const size_t need = carve_occ(B, N, Nf, off, off_occ);
+  if (ws_bytes < need)
+    return set_error(NERF_ERR_WORKSPACE, "nerf_render_rays_occ: workspace %zu < %zu bytes", ws_bytes, need);
+  char* ws = (char*)workspace;
+  auto region = [&](int i) { return (float*)(ws + off[i]); };
+  float* dn = region(W_DIRS);
+  float* z = (Nf == 0 && z_out) ? z_out : region(W_Z);
+  float* feat = region(W_FEAT);
+  float* rgb_c = region(W_RGBC);
+  float* sigma_c = region(W_SIGC);
+  float* wc = (Nf == 0) ? weights_out : region(W_WC);
+  float* z_all = z_out ? z_out : region(W_ZALL);
+  float* maps = region(W_MAPS);
+  int* live = (int*)(ws + off_occ[WO_LIVE]);
+  int* count = (int*)(ws + off_occ[WO_COUNT]);
+  uint32_t* blocks = (uint32_t*)(ws + off_occ[WO_BLOCKS]);
+  const uint64_t seed_c = rng_key_at(seed, (uint64_t)ray0 * (uint64_t)N);
+  const uint64_t seed_f = rng_key_at(seed ^ 0x5DEECE66Dull, (uint64_t)ray0 * (uint64_t)Nf);
+  const bool gathered = g_mlp_arith == NERF_ARITH_F16X3;
+  // one MLP stage over the (B, n) samples at zz
+  auto masked_mlp = [&](const float* zz, int n, float* rgb, float* sigma) -> int {
+    int rc;
+    if (gathered) {
+      if ((rc = launch_occ_classify(rays_o, dn, zz, B, n, bits, G, lo, inv, live, count, nullptr, sigma, rgb, blocks,
+                                    s)))
+        return rc;
+      return profiled_mlp_live(packed, rays_o, dn, zz, B, n, feat, rgb, sigma, live, count, s);
+    }
+    if ((rc = profiled_mlp(packed, rays_o, dn, zz, B, n, feat, rgb, sigma, nullptr, 0, s))) return rc;
+    return launch_occ_classify(rays_o, dn, zz, B, n, bits, G, lo, inv, live, count, nullptr, sigma, rgb, blocks, s);
+  };
+  int rc;
+  if ((rc = launch_ray_features(packed, rays_d, B, app, app_rows, feat, s, nullptr, dn))) return rc;
+  if ((rc = launch_stratified(rays_o, dn, B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand, seed_c,
+                              z, nullptr, s)))
+    return rc;
+  if ((rc = masked_mlp(z, N, rgb_c, sigma_c))) return rc;
+  if (Nf == 0) return launch_composite(rgb_c, sigma_c, z, B, N, rgb_map, depth_map, wc, s);
+  float* crgb = coarse_rgb ? coarse_rgb : maps;
+  float* cdepth = coarse_depth ? coarse_depth : maps + 3 * B;
+  if ((rc = launch_composite(rgb_c, sigma_c, z, B, N, crgb, cdepth, wc, s))) return rc;
+  float* z_fine = region(W_ZF);
+  uint16_t* msrc = (uint16_t*)region(W_SRC);
+  float* rgb_f = region(W_RGBF);
+  float* sigma_f = region(W_SIGF);
+  if ((rc = launch_importance(nullptr, nullptr, z, wc, B, N, Nf, u_lin, u_rand, seed_f, z_all, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, z_fine, nullptr, s, msrc)))
+    return rc;
+  if ((rc = masked_mlp(z_fine, Nf, rgb_f, sigma_f))) return rc;
+  return launch_composite_merged(rgb_c, sigma_c, rgb_f, sigma_f, msrc, z_all, B, N, Nf, rgb_map, depth_map,
+                                 weights_out, s);
+}
+
+int nerf_render_rays_occ(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
+                         double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
+                         const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0, const float* app,
+                         int64_t app_rows, const uint32_t* bits, int G, const float* lo, const float* inv,
+                         float* rgb_map, float* depth_map, float* weights_out, float* z_out, float* coarse_rgb,
+                         float* coarse_depth, void* workspace, size_t ws_bytes, nerf_stream_t stream) {
+  REQUIRE(B >= 0 && ray0 >= 0, "nerf_render_rays_occ: B=%lld ray0=%lld", (long long)B, (long long)ray0);
+  if (N < 1 || N > 4096 || Nf < 0 || N + Nf > 4096 || (Nf > 0 && (N > 256 || Nf > 1024)))
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_render_rays_occ: N=%d Nf=%d outside the supported range", N, Nf);
+  REQUIRE(bits && lo && inv, "nerf_render_rays_occ: null grid");
+  REQUIRE_GRID("nerf_render_rays_occ", G);
+  REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "nerf_render_rays_occ: app_rows=%lld with B=%lld",
+          (long long)app_rows, (long long)B);
+  const int64_t chunk = nerf_render_chunk_rays(N, Nf);
+  if (chunk < 1)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_render_rays_occ: N=%d Nf=%d exceed the launch limit", N, Nf);
+  const int64_t T = Nf > 0 ? (int64_t)N + Nf : (int64_t)N;
+  for (int64_t c0 = 0; c0 < B; c0 += chunk) {
+    const int64_t n = B - c0 < chunk ? B - c0 : chunk;
+    const bool per_ray_app = app_rows > 1;
+    if (int rc = render_rays_occ_chunk(
+            packed, rays_o + 3 * c0, rays_d + 3 * c0, n, near, far, N, Nf, t_vals, u_lin, perturb,
+            t_rand ? t_rand + c0 * N : nullptr, u_rand ? u_rand + c0 * Nf : nullptr, seed, ray0 + c0,
+            per_ray_app ? app + c0 * kAppDim : app, per_ray_app ? n : app_rows, bits, G, lo, inv, rgb_map + 3 * c0,
+            depth_map + c0, weights_out ? weights_out + c0 * T : nullptr, z_out ? z_out + c0 * T : nullptr,
+            coarse_rgb ? coarse_rgb + 3 * c0 : nullptr, coarse_depth ? coarse_depth + c0 : nullptr, workspace,
+            ws_bytes, (hipStream_t)stream))
+      return rc;
+  }
+  return NERF_OK;
+}
+
 }  // extern "C"

@@ -160,6 +160,18 @@ int launch_mlp16(const float* packed, const float* o, const float* d, const floa
 // the render MLP on 16 x 16 x 32 tiles (mlp16s.hip): launch_mlp16 without saves
 int launch_mlp16s(const float* packed, const float* o, const float* d, const float* z, int64_t R, int N,
                   const float* feat, float* rgb, float* sigma, const int* out_slot, int out_T, hipStream_t s);
+// the same kernel on the samples named by a device-side live list (occupancy.hip builds it)
+int launch_mlp16s_live(const float* packed, const float* o, const float* d, const float* z, int64_t R, int N,
+                       const float* feat, float* rgb, float* sigma, const int* live, const int* live_count,
+                       hipStream_t s);
+// occupancy grid (occupancy.hip): classify + compact (block_counts: occ_block_count_bytes(B n) bytes;
+// mask, sigma_zero, rgb_zero nullable), threshold + pack, dilation
+size_t occ_block_count_bytes(int64_t M);
+int launch_occ_classify(const float* o, const float* d, const float* z, int64_t B, int n, const uint32_t* bits, int G,
+                        const float* lo, const float* inv, int* live, int* live_count, uint8_t* mask,
+                        float* sigma_zero, float* rgb_zero, uint32_t* block_counts, hipStream_t s);
+int launch_occ_pack(const float* lattice, int G, int sp, float thr, uint32_t* bits, hipStream_t s);
+int launch_occ_dilate(const uint32_t* in, int G, uint32_t* out, hipStream_t s);
 int launch_mlp(const float* packed, const float* o, const float* d, const float* z, int64_t R,
                int N, const float* feat, float* rgb, float* sigma, const int* out_slot, int out_T,
                hipStream_t s, float* save = nullptr, const float* encd = nullptr, uint32_t* masks = nullptr);

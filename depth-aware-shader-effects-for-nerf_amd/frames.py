@@ -102,12 +102,13 @@ def render_frames_sharded(ray_fn, render_fn, H, W, n_frames, group=None, device=
 
 @torch.no_grad()
 def render_path_frames(model, poses, H, W, focal, near, far, n_samples, n_importance=0, appearance_embedding=None,
-                       perturb=False, hierarchical=False, seed=0, group=None, timing=None, virtual_shards=None):
+                       perturb=False, hierarchical=False, seed=0, group=None, timing=None, virtual_shards=None,
+                       occupancy=None):
     """render_frames_sharded with nerfmi's HIP get_rays / render_rays (one list entry per frame:
     a (3,4)/(4,4) c2w, kept on the host: ray generation takes the pose by value, so no shard
     synchronises on a device-to-host copy).  The in-kernel draws are keyed by `seed` and the global
     ray index, so the frames are bit-identical for every world size.  timing: passed to
-    render_rays (per-launch MLP events)."""
+    render_rays (per-launch MLP events); occupancy: an OccupancyGrid, passed to render_rays."""
     from . import _lib
     from .ray_utils import rays_on_device
     from .render import render_rays
@@ -121,7 +122,7 @@ def render_path_frames(model, poses, H, W, focal, near, far, n_samples, n_import
         rgb, depth, _ = render_rays(model, o, d, near, far, n_samples, n_importance,
                                     appearance_embedding=appearance_embedding, perturb=perturb,
                                     hierarchical=hierarchical, seed=int(seed) & (2 ** 62 - 1), ray_offset=offset,
-                                    timing=timing)
+                                    timing=timing, **({} if occupancy is None else {"occupancy": occupancy}))
         return rgb, depth
 
     return render_frames_sharded(ray_fn, render_fn, H, W, len(c2ws), group=group, device=dev,

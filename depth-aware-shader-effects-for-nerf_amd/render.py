@@ -22,6 +22,10 @@ and ``background_color``.  Keyword-only extras:
   staged, reuse_coarse  staged=True runs the per-stage entry points instead of the single
                       nerf_render_rays call; reuse_coarse=False (staged only) re-evaluates the
                       coarse samples in the fine pass — bit-identical, for the tests.
+  occupancy           an OccupancyGrid (occupancy.py; not a reference feature): the sigma of every
+                      sample outside the grid's set cells is 0 and the MLP is not run on it
+                      (nerf_render_rays_occ).  Inference only, single-call path only: combined with
+                      gradients, staged=True or timing= it raises ValueError.
 ``render_rays`` is the same function (the north-star name).
 
 With gradients enabled and a trainable model (or an appearance embedding that requires grad),
@@ -57,8 +61,18 @@ def packed_for(model):
 
 def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, appearance_embedding=None,
                   background_color=None, perturb=True, *, hierarchical=False, t_rand=None, u_rand=None,
-                  seed=None, ray_offset=0, timing=None, staged=False, reuse_coarse=True):
+                  seed=None, ray_offset=0, timing=None, staged=False, reuse_coarse=True, occupancy=None):
     from . import autograd
+    if occupancy is not None:
+        from .occupancy import OccupancyGrid
+        if not isinstance(occupancy, OccupancyGrid):
+            raise ValueError(f"nerfmi.volume_render(occupancy=): expected an OccupancyGrid, got {type(occupancy).__name__}")
+        grad = autograd.needs_grad(model, appearance_embedding if uses_appearance(model) else None, rays_o, rays_d)
+        if grad or staged or timing is not None:
+            what = "gradients enabled" if grad else ("staged=True" if staged else "timing=")
+            raise ValueError(f"nerfmi.volume_render(occupancy=) with {what}: sample skipping is an inference "
+                             f"feature of the single-call path (render under torch.no_grad(), without staged / "
+                             f"timing)")
     if autograd.needs_grad(model, appearance_embedding if uses_appearance(model) else None, rays_o, rays_d):
         if hierarchical or staged or timing is not None:
             what = "hierarchical=True" if hierarchical else ("staged=True" if staged else "timing=")
@@ -95,7 +109,25 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
     if Nf:
         crgb = torch.empty(B, 3, device=dev)
         cdepth = torch.empty(B, 1, device=dev)
-    if timing is None and not staged:
+    if occupancy is not None:
+        if occupancy.bits.device != dev:
+            raise ValueError(f"nerfmi.volume_render(occupancy=): the grid is on {occupancy.bits.device}, the render "
+                             f"runs on {dev}")
+        if occupancy.bits.dtype != torch.int32 or occupancy.bits.numel() != occupancy.words:
+            raise ValueError(f"nerfmi.volume_render(occupancy=): bits must be {occupancy.words} int32 words, got "
+                             f"{occupancy.bits.numel()} of {occupancy.bits.dtype}")
+        ws = torch.empty(lib.nerf_render_occ_workspace_bytes(B, N, Nf), dtype=torch.uint8, device=dev)
+        _lib.check(lib.nerf_render_rays_occ(
+            _lib.ptr(packed), _lib.ptr(o), _lib.ptr(d), B, float(near), float(far), N, Nf, _lib.ptr(t_vals),
+            _lib.ptr(u_lin), int(bool(perturb)), _lib.ptr(tr), _lib.ptr(ur), seed or 0, int(ray_offset),
+            _lib.ptr(app), rows, _lib.ptr(occupancy.bits.contiguous()), occupancy.resolution, occupancy.c_lo(),
+            occupancy.c_inv(),
+            _lib.ptr(rgb_map), _lib.ptr(depth_map), _lib.ptr(weights), _lib.ptr(z_vals),
+            _lib.ptr(crgb) if Nf else None, _lib.ptr(cdepth) if Nf else None, _lib.ptr(ws), ws.numel(),
+            _lib.stream()), "nerf_render_rays_occ")
+        if Nf:
+            cw, cz = None, None
+    elif timing is None and not staged:
         ws = torch.empty(lib.nerf_render_workspace_bytes(B, N, Nf), dtype=torch.uint8, device=dev)
         _lib.check(lib.nerf_render_rays(
             _lib.ptr(packed), _lib.ptr(o), _lib.ptr(d), B, float(near), float(far), N, Nf, _lib.ptr(t_vals),

@@ -196,6 +196,65 @@ int nerf_render_rays(const float* packed, const float* rays_o, const float* rays
                      float* coarse_depth, void* workspace, size_t ws_bytes,
                      nerf_stream_t stream);
 
+/* --------------------------------------------------------- occupancy grid
+ * Sample skipping (not a reference feature; additions to ABI 11, nothing above changes).
+ * A grid is an axis-aligned box lo[3], hi[3], G cells per axis (1..1024) and G^3 bits: cell
+ * (ix, iy, iz) has index (iz*G + iy)*G + ix and is bit (index & 31) of uint32 word (index >> 5);
+ * nerf_occupancy_words(G) words (0 for G outside 1..1024).  lo and inv are HOST arrays of 3 floats,
+ * inv[c] = (float)(G / ((double)hi[c] - (double)lo[c])).
+ * A sample at p = o + d*z (two roundings, as nerf_mlp_forward forms it) is LIVE iff for every axis
+ * t_c = (p_c - lo_c) * inv_c (one subtraction, one multiplication, each rounded, no FMA) has
+ * t_c >= 0 and t_c < G (float compares: NaN is dead) and the bit of cell ((int)t_x, (int)t_y,
+ * (int)t_z) is set; otherwise it is DEAD.
+ * Rendering with a grid is the plain render with the sigma of every dead sample replaced by 0
+ * before compositing, in the coarse pass and (Nf > 0) over the Nf new samples of the fine pass, which
+ * are resampled from the masked coarse weights.  A dead sample has weight exactly 0 (weights_out
+ * holds 0 there) and multiplies the transmittance by 1 + 1e-10 as a sigma = 0 sample does; z_out
+ * is unchanged.  Under NERF_ARITH_F16X3 the MLP is not evaluated on dead samples (per-sample
+ * results do not depend on a sample's place in a launch, so the result is bit-identical to
+ * masking nerf_mlp_forward's sigma and compositing); under NERF_ARITH_F32 every sample is
+ * evaluated by the f32 kernel and the dead rows are zeroed afterwards: the same contract, no
+ * speed-up.
+ *   nerf_occupancy_pack      bit of a cell = (max over its s^3 probes of the (s*G)^3 density lattice,
+ *                            index (z*sG + y)*sG + x, NaN probes ignored) > threshold.  s >= 1.
+ *   nerf_occupancy_dilate    3x3x3 binary dilation, clamped at the box faces; not in place.
+ *   nerf_occupancy_classify  rays_o (B,3), normalised dirs (B,3), z (B,n) -> live: the indices
+ *                            r*n + s of the live samples, ascending (room for B*n int32);
+ *                            *live_count (device int32); mask (B,n) uint8, 1 = live, nullable.
+ *                            B*n <= the launch limit (nerf_render_chunk_rays).  workspace:
+ *                            nerf_occupancy_classify_workspace_bytes(B, n) device bytes.
+ *   nerf_mlp_forward_live    nerf_mlp_forward (z_vals required, no out_slot) on the samples named by
+ *                            live[0 .. *live_count): rows live[i] of rgb / sigma are written, every
+ *                            other row is left untouched.  The count is read on the device: no
+ *                            copy to the host, no synchronisation.  F16X3 only (UNSUPPORTED under
+ *                            F32); R*N <= the launch limit.
+ *   nerf_render_rays_occ     nerf_render_rays' arguments plus the grid; same chunking and errors.
+ *                            workspace: nerf_render_occ_workspace_bytes(B, N, Nf).
+ * nerf_profile_mlp_* records the gathered launches too, with the launch's R*N as sample count (the
+ * live count stays on the device). */
+size_t nerf_occupancy_words(int G);
+int nerf_occupancy_pack(const float* sigma_lattice, int G, int s, float threshold, uint32_t* bits,
+                        nerf_stream_t stream);
+int nerf_occupancy_dilate(const uint32_t* bits_in, int G, uint32_t* bits_out, nerf_stream_t stream);
+size_t nerf_occupancy_classify_workspace_bytes(int64_t B, int n);
+int nerf_occupancy_classify(const float* rays_o, const float* dirs, const float* z, int64_t B, int n,
+                            const uint32_t* bits, int G, const float* lo, const float* inv,
+                            int32_t* live, int32_t* live_count, uint8_t* mask, void* workspace,
+                            size_t ws_bytes, nerf_stream_t stream);
+int nerf_mlp_forward_live(const float* packed, const float* origins, const float* dirs,
+                          const float* z_vals, int64_t R, int N, const float* ray_feat,
+                          const int32_t* live, const int32_t* live_count, float* rgb, float* sigma,
+                          nerf_stream_t stream);
+size_t nerf_render_occ_workspace_bytes(int64_t B, int N, int Nf);
+int nerf_render_rays_occ(const float* packed, const float* rays_o, const float* rays_d, int64_t B,
+                         double near, double far, int N, int Nf, const float* t_vals,
+                         const float* u_lin, int perturb, const float* t_rand, const float* u_rand,
+                         uint64_t seed, int64_t ray0, const float* app, int64_t app_rows,
+                         const uint32_t* bits, int G, const float* lo, const float* inv,
+                         float* rgb_map, float* depth_map, float* weights_out, float* z_out,
+                         float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
+                         nerf_stream_t stream);
+
 /* ------------------------------------------------- depth-aware post effects
  * The depth-reading effects of the reference's PostProcessor (src/post_processor.py) on the
  * frame run.py renders.  image / out: uint8 (H,W,3) RGB; depth: fp32 (H,W)

@@ -11,7 +11,9 @@ rgb_{i:03d}.png (uint8 by truncation, run.py:233), a viridis depth_{i:03d}.png
 Added flags: --random_init SEED renders a seeded random-init model when no checkpoint exists
 (none does in this environment); --hierarchical enables the H1 fine pass (the reference
 ignores n_importance, render.py:83-86) with --n_importance samples; --chunk renders the frame
-in ray chunks (0 = whole frame per call).  Under torchrun every frame is ray-sharded across
+in ray chunks (0 = whole frame per call); --occupancy RES builds an occupancy grid of RES^3 cells over
+[-X, X]^3 (--occupancy_bound X, default 1.5) from the loaded model once and skips the samples outside
+its set cells in every frame (nerfmi.OccupancyGrid; not a reference feature).  Under torchrun every frame is ray-sharded across
 the ranks (frames.py) and rank 0 writes the images.
 --mode train runs the reference's training loop (run.py:326-347 -> src/train.py) on the nerfmi
 kernels (nerfmi.train.train_nerf; the nerf_synthetic scene when present, else the
@@ -72,6 +74,9 @@ def parse_args(argv=None):
     p.add_argument('--hierarchical', action='store_true', help='H1 fine pass with --n_importance samples')
     p.add_argument('--n_importance', type=int, default=None, help='fine samples (default Config.num_importance)')
     p.add_argument('--chunk', type=int, default=0, help='rays per render call (0 = whole frame)')
+    p.add_argument('--occupancy', type=int, default=0, metavar='RES',
+                   help='occupancy-grid resolution for sample skipping (0 = off)')
+    p.add_argument('--occupancy_bound', type=float, default=1.5, metavar='X', help='the grid covers [-X, X]^3')
     p.add_argument('--seed', type=int, default=0, help='seed of the in-kernel sampling RNG')
     p.add_argument('--iterations', type=int, default=None, help='training iterations (default Config)')
     p.add_argument('--save_dir', type=str, default='checkpoints',
@@ -109,7 +114,7 @@ class SceneInfo:
 def render_path(model, scene, config, output_dir, num_frames=120, quality='high', width=800, height=800,
                 start_frame=0, end_frame=None, save_depth=False, raw_output=False, camera_path='circle',
                 spiral_loops=2.0, height_range=(-0.5, 0.5), hierarchical=False, n_importance=None, chunk=0,
-                seed=0, shader=None):
+                seed=0, shader=None, occupancy=None):
     """run.py:63-282 (render mode) on nerfmi."""
     import torch.distributed as dist
     from nerfmi import cameras, frames
@@ -135,6 +140,8 @@ def render_path(model, scene, config, output_dir, num_frames=120, quality='high'
         cam = cameras.camera_position(camera_path, theta[i], heights[i], phi[i])
         c2w = torch.tensor(cameras.look_at_c2w(cam, center, up), dtype=torch.float32)
         kw = dict(appearance_embedding=app, perturb=perturb, hierarchical=hierarchical)
+        if occupancy is not None:
+            kw["occupancy"] = occupancy
         if world > 1 or not chunk:
             rgb, depth = frames.render_path_frames(model, [c2w], height, width, focal, scene.near, scene.far,
                                                    n_samples, n_imp, seed=seed + frame_idx, **kw)
@@ -261,13 +268,21 @@ def main(argv=None):
         if config.use_appearance and ckpt.get('appearance_embeddings') is not None:
             scene.appearance_embeddings = ckpt['appearance_embeddings']
     model = model.cuda()
+    occupancy = None
+    if args.occupancy:
+        x = float(args.occupancy_bound)
+        with torch.no_grad():
+            occupancy = nerfmi.OccupancyGrid.from_model(model, (-x,) * 3, (x,) * 3, resolution=args.occupancy)
+        if rank == 0:
+            print(f"Occupancy grid {args.occupancy}^3 over [-{x:g}, {x:g}]^3: {occupancy.fraction():.4f} of the "
+                  f"cells are set")
     with torch.no_grad():
         render_path(model, scene, config, args.output_dir, num_frames=args.frames, quality=args.quality,
                     width=args.width, height=args.height, start_frame=args.start_frame, end_frame=args.end_frame,
                     save_depth=args.save_depth, raw_output=args.raw_output, camera_path=args.camera_path,
                     spiral_loops=args.spiral_loops, height_range=args.height_range,
                     hierarchical=args.hierarchical, n_importance=args.n_importance, chunk=args.chunk,
-                    seed=args.seed, shader=shader)
+                    seed=args.seed, shader=shader, occupancy=occupancy)
     if group is not None:
         dist.destroy_process_group()
     return 0
