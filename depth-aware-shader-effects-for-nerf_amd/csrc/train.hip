@@ -34,7 +34,11 @@ static_assert(kSaveRow == NERF_SAVE_ROW && kGradRow == NERF_GRAD_ROW, "nerfmi_tr
 // instead (autograd: grad_map (B,3) for rgb_map, grad_depth (B) for depth_map, each nullable = 0),
 // g = grad_map[r] and the depth term of depth = S / (A + 1e-10), S = sum w z, A = sum w (:80) adds
 //   dw_s += gd (z_s - S / (A + 1e-10)) / (A + 1e-10)
-// with S and A re-accumulated (double) over the same float weights in the forward pass.
+// with S and A re-accumulated in the forward pass.  dw, T, w and d a stay in double and d sigma is
+// rounded once: d a_s is a difference of two terms of the size of dw (an empty sample in front of a
+// surface: dw_s - sum dw_t w_t), and float roundings of dw, w and T there put d sigma twice as far from
+// the float64 gradient as torch's fp32 autograd (tests/test_gpu_degenerate_rays.py).  drgb is the
+// forward's float weight times g.
 __global__ void __launch_bounds__(256)
 composite_backward_kernel(const float* __restrict__ rgb, const float* __restrict__ sigma, const float* __restrict__ zv,
                           const float* __restrict__ rgb_map, const float* __restrict__ target,
@@ -92,9 +96,9 @@ composite_backward_kernel(const float* __restrict__ rgb, const float* __restrict
     if (gd != 0.0f) {
       double excl = __shfl_up(incl, 1);
       if (lane == 0) excl = 1.0;
-      const float w = alpha * (float)(carry * excl);
-      wz += (double)w * (double)z;
-      ws += (double)w;
+      const double w = (double)alpha * (carry * excl);
+      wz += w * (double)z;
+      ws += w;
     }
     if (lane == 0) carry_chunk[c] = carry;
     carry *= __shfl(incl, 63);
@@ -106,7 +110,7 @@ composite_backward_kernel(const float* __restrict__ rgb, const float* __restrict
       wz += __shfl_xor(wz, off);
       ws += __shfl_xor(ws, off);
     }
-    const double den = (double)((float)ws + 1e-10f);
+    const double den = ws + (double)1e-10f;
     dinv = 1.0 / den;
     dmean = wz * dinv;
   }
@@ -134,20 +138,20 @@ composite_backward_kernel(const float* __restrict__ rgb, const float* __restrict
     }
     double excl = __shfl_up(incl, 1);
     if (lane == 0) excl = 1.0;
-    const float T = (float)(carry_chunk[c] * excl);
-    const float w = alpha * T;
-    float dw = 0.0f;
+    const double T = carry_chunk[c] * excl;
+    const float w = alpha * (float)T;                      // the forward's weight (composite.hip)
+    double dw = 0.0;
     if (valid) {
       const int64_t e3 = 3 * (base + s);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        dw += g[k] * rgb[e3 + k];
+        dw += (double)g[k] * (double)rgb[e3 + k];
         drgb[e3 + k] = w * g[k];
       }
-      if (gd != 0.0f) dw += (float)((double)gd * ((double)z - dmean) * dinv);
+      if (gd != 0.0f) dw += (double)gd * ((double)z - dmean) * dinv;
     }
     // exclusive suffix sum of dw*w inside the chunk, plus the chunks after it
-    double v = valid ? (double)dw * (double)w : 0.0;
+    double v = valid ? dw * ((double)alpha * T) : 0.0;
     double incl_rev = v;                                   // inclusive suffix within the chunk
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -156,8 +160,8 @@ composite_backward_kernel(const float* __restrict__ rgb, const float* __restrict
     }
     const double excl_rev = incl_rev - v + suffix;
     if (valid) {
-      const float da = (float)((double)dw * (double)T - excl_rev / (double)fs);
-      dsigma[base + s] = da * dist * e;
+      const double da = dw * T - excl_rev / (double)fs;
+      dsigma[base + s] = (float)(da * (double)dist * (double)e);
     }
     suffix += __shfl(incl_rev, 0);
   }
