@@ -34,8 +34,14 @@
 // read into its own 16 registers one chunk ahead: tile 3's at the chunk's segment 0, tiles 0-2 of the
 // next chunk in segments 1-3, each right after the registers' last MFMAs; the next chunk is published
 // (counted vmcnt + barrier, as stream16.h) after segment 0 and the chunk three ahead is DMA'd in
-// segments 1-3.  The previous layer's epilogue (the side work) runs a quarter (one 16 x 16 tile of one
-// sample tile: 4 values) per segment in the MFMA shadow, on mlp16's group schedule.
+// segments 1-3: wave w moves the chunk's four consecutive 1 KiB pieces 4w .. 4w+3 from one address
+// pair and one M0 write, the pieces told apart by the instruction's immediate offset (sdma_piece).
+// The previous layer's epilogue (the side work) runs in the MFMA shadow.  In the plain trunk (layers
+// 1-3, 5-6 and layer 7's group A) it runs as half-quarters (two values of a 16 x 16 tile of one
+// sample tile), one per segment, placed by hand at no more than two VALU instructions per MFMA gap
+// and with no packed-f32 instruction (ssegment_h, shalf).  Layer 0, the skip layer, layer 7's group
+// B and the colour layer, whose segments also carry PE work, keep a quarter (4 values) per segment
+// on mlp16's group schedule (ssegment, squarter).
 //
 // Block loop.  The grid is one workgroup per CU; workgroup b runs the 128-sample blocks b, b + grid,
 // ...  Biases, constants and the rgb head are staged in LDS once per workgroup.  The weight ring does
@@ -107,6 +113,54 @@ __device__ __forceinline__ void sread_tile(const float* slot, const uint32_t (&o
       a[r][part] = __builtin_bit_cast(h16x8, *reinterpret_cast<const f32x4*>(slot + off[r] + TI * 512 + part * 256));
 }
 
+// Fragment K (row half K >> 1, hi / lo K & 1) of tile TI: sread_tile's reads one at a time
+template <int TI, int K>
+__device__ __forceinline__ void sread_frag(const float* slot, const uint32_t (&off)[2], STile& a) {
+  constexpr int r = K >> 1, part = K & 1;
+  a[r][part] = __builtin_bit_cast(h16x8, *reinterpret_cast<const f32x4*>(slot + off[r] + TI * 512 + part * 256));
+}
+
+// ---- the render kernel's weight DMA --------------------------------------------------------
+// Wave w moves the four consecutive 1 KiB pieces 4w .. 4w+3 of a chunk (stream16.h's chunk_dma_piece
+// gives it w, w+4, w+8, w+12: an M0 write, its wait state and a 64-bit address per piece, 16 scalar
+// instructions per chunk-step on the issue port of the SIMD's only wave).  The instruction's
+// immediate offset moves the global address and the LDS destination together (LDS address = M0 +
+// offset + 16 lane; scripts/microbench/lds_dma_offset.hip checks it on the device), so piece I is
+// offset:1024 I from one SGPR pair and one M0 value per chunk: piece 0 writes M0, pieces 1-3 read
+// what it left.  That holds while nothing writes M0 between a chunk's pieces: the feature-row DMA
+// restores it, and scripts/check_isa.py checks the built kernel (its "held M0" rule).
+// lds_base: the ring's LDS byte address + kSDmaWave * wave; voff = 16 lane + kSDmaWave * wave.
+#ifdef NERF16S_PIECE_DMA   // A/B build: stream16.h's assignment
+constexpr uint32_t kSDmaWave = 1024;
+template <int SLOT, int I>
+__device__ __forceinline__ void sdma_piece(const float* __restrict__ stream, int c, uint32_t lds_base, uint32_t voff) {
+  chunk_dma_piece<SLOT, I>(stream, c, lds_base, voff);
+}
+#else
+constexpr uint32_t kSDmaWave = 4096;
+template <int SLOT, int I>
+__device__ __forceinline__ void sdma_piece(const float* __restrict__ stream, int c, uint32_t lds_base, uint32_t voff) {
+  const char* src = reinterpret_cast<const char*>(stream) + (size_t)c * (kChunkFloats * 4);
+  if constexpr (I == 0)
+    asm volatile(
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %0, %1"
+        :
+        : "v"(voff), "s"(src), "s"(lds_base + SLOT * (kChunkFloats * 4))
+        : "memory", "m0");
+  else
+    asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" : : "v"(voff), "s"(src), "n"(I * 1024) : "memory");
+}
+#endif
+template <int SLOT>
+__device__ __forceinline__ void sdma_chunk(const float* __restrict__ stream, int c, uint32_t lds_base, uint32_t voff) {
+  sdma_piece<SLOT, 0>(stream, c, lds_base, voff);
+  sdma_piece<SLOT, 1>(stream, c, lds_base, voff);
+  sdma_piece<SLOT, 2>(stream, c, lds_base, voff);
+  sdma_piece<SLOT, 3>(stream, c, lds_base, voff);
+}
+
 // Tile TI's 12 MFMAs: per (row half, sample tile) lo(W)hi(a), hi(W)lo(a), hi(W)hi(a) chained.
 // hook(j) after chain j (the DMA pieces).
 template <int G, int TI, bool FIRST, typename Hook>
@@ -149,8 +203,49 @@ __device__ __forceinline__ void ssegment(const STile& a, const Operand& b0, cons
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// The plain trunk's tile segment (layers 1-3, 5-6, layer 7's group A), placed by hand: every MFMA gap
+// is fenced, so what a gap holds is what is written here.  The side work comes as half-quarters (two
+// values of a quarter, 10 VALU in 6 units of at most two: shalf below), one per segment, at most two
+// VALU per gap, in gaps that carry neither a fragment read (1-4) nor a DMA piece (2, segment 1's 8):
+// an MFMA holds the issue port for 8 of its 16 cycles and a VALU instruction for 4, so a third
+// instruction in a gap lengthens it.  The quarter schedule above put six per gap into four gaps
+// of every other segment (its 40-VALU budget against the ~20 the quarter has).  A group has 32
+// halves and 28 segments that may carry one; four segments carry two, one gap apart (and then in
+// the gap of a DMA piece too).
+// side(slot, unit): unit -1 the half's LDS read, 0..5 its VALU units; slot 0, 1 the segment's halves.
+// the unit (or -2) in `gap`: a lone half in gaps 5, 6, 7, 9, 10, 11; a segment's two halves in gaps
+// 5-10 and 6-11, a unit apart, so that no gap holds the same instruction of both
+__device__ __forceinline__ constexpr int shalf_unit_at(int gap, int slot, bool two) {
+  if (two) return gap >= 5 + slot && gap <= 10 + slot ? gap - 5 - slot : -2;
+  return slot ? -2 : (gap >= 5 && gap <= 7 ? gap - 5 : (gap >= 9 && gap <= 11 ? gap - 6 : -2));
+}
+template <int G, int TI, bool FIRST, int NRD, bool TWO, typename Frag, typename Side, typename Hook>
+__device__ __forceinline__ void ssegment_h(const STile& a, const Operand& b0, const Operand& b1, SAcc& acc, Frag&& frag,
+                                           Side&& side, Hook&& hook) {
+  using Slot0 = std::integral_constant<int, 0>;
+  using Slot1 = std::integral_constant<int, 1>;
+  side(Slot0{}, std::integral_constant<int, -1>{});
+  side(Slot1{}, std::integral_constant<int, -1>{});
+  __builtin_amdgcn_sched_barrier(0);
+  static_for<12>([&](auto ic) __attribute__((always_inline)) {
+    constexpr int i = decltype(ic)::value, j = i / 3, k = i % 3, r = j >> 1, st = j & 1;
+    const Operand& b = st ? b1 : b0;
+    f32x4& c = acc[4 * G + TI][r][st];
+    if constexpr (k == 0) c = FIRST ? mfma16s(a[r][1], b.hi, f32x4{}) : mfma16s(a[r][1], b.hi, c);
+    if constexpr (k == 1) c = mfma16s(a[r][0], b.lo, c);
+    if constexpr (k == 2) {
+      c = mfma16s(a[r][0], b.hi, c);
+      hook(std::integral_constant<int, j>{});
+    }
+    if constexpr (i >= 1 && i <= 4 * NRD) frag(std::integral_constant<int, i - 1>{});
+    side(Slot0{}, std::integral_constant<int, shalf_unit_at(i, 0, TWO)>{});
+    side(Slot1{}, std::integral_constant<int, shalf_unit_at(i, 1, TWO)>{});
+    __builtin_amdgcn_sched_barrier(0);
+  });
+}
+
 // Side-work schedules, by (chunk i of the group, segment): which quarter (or PE operand) runs there.
-enum SSide { kSNone, kSPrev, kSCur, kSL0, kSSkipPrev, kSSkipCur, kSPrevPe, kSCurPe };
+enum SSide { kSNone, kSPrev, kSCur, kSL0, kSSkipPrev, kSSkipCur, kSPrevPe, kSCurPe, kSPrevH, kSCurH };
 // The skip layer's PE operands (k-steps 8, 9; two sample tiles each) are split from the wave's LDS
 // copy just before each group reads them: k-step 8's in chunk 7 (segments 0, 2), 9's in chunk 8
 // (segments 0, 2), so they hold registers only while read (the rest of the layer needs all of in[]).
@@ -176,6 +271,29 @@ __device__ __forceinline__ constexpr int sq_cur(int i, int seg) {
   if (cnt[i] == 3) return seg >= 1 ? base[i] + seg - 1 : -1;
   return seg == 1 ? base[i] : (seg == 3 ? base[i] + 1 : -1);
 }
+// The same two sides in half-quarters (kSPrevH, kSCurH; half h = quarter h >> 1's values 2 (h & 1),
+// + 1), under the same two constraints.  Group A: two per segment in chunk 0, one in every segment of
+// chunks 1-6.  Group B: one in every segment of chunks 1-6, two per segment in chunk 7.
+__device__ __forceinline__ constexpr int sh_prev(int i, int seg, int slot) {
+  if (i == 0) return 2 * seg + slot;
+  return i >= 7 || slot ? -1 : 8 + 4 * (i - 1) + seg;
+}
+__device__ __forceinline__ constexpr int sh_cur(int i, int seg, int slot) {
+  if (i == 7) return 24 + 2 * seg + slot;
+  return i == 0 || i >= 8 || slot ? -1 : 4 * (i - 1) + seg;
+}
+__device__ __forceinline__ constexpr bool sh_schedules_hold() {
+  int np = 0, nc = 0;
+  for (int i = 0; i < 8; ++i)
+    for (int seg = 0; seg < 4; ++seg)
+      for (int slot = 0; slot < 2; ++slot) {
+        const int hp = sh_prev(i, seg, slot), hc = sh_cur(i, seg, slot);
+        if (hp >= 0 && (hp != np++ || i >= 4 + hp / 8)) return false;   // tile 4+j converted before chunk 4+j
+        if (hc >= 0 && (hc != nc++ || i <= hc / 8)) return false;       // tile T only after chunk T
+      }
+  return np == 32 && nc == 32;
+}
+static_assert(sh_schedules_hold(), "half-quarter schedules: each half once, in order, inside its window");
 // The next block's positional encoding (32 values per lane) runs one value per segment in the 32
 // segments of layer 7's group B and of the colour layer (8 chunks each) that carry no quarter: value
 // 0..15 in group B's free segments in order, 16..31 in the colour layer's.
@@ -203,6 +321,25 @@ __device__ __forceinline__ constexpr int svpg(int i, int seg) {
   return n == 0 ? 0 : (n * 40 + 11 - kSValuGap0) / (12 - kSValuGap0);   // ~40 VALU per quarter
 }
 
+// Segment TI of chunk I under side schedule KIND: the hand-placed segment for the half-quarter
+// schedules, the group-scheduled one for the rest.  frag(K) reads fragment K of the segment's tile.
+template <int G, int TI, bool FIRST, int NRD, int KIND, int I, typename Frag, typename Side, typename Hook>
+__device__ __forceinline__ void sseg(const STile& a, const Operand& b0, const Operand& b1, SAcc& acc, Frag&& frag,
+                                     Side&& side, Hook&& hook) {
+  using IC = std::integral_constant<int, I>;
+  using SC = std::integral_constant<int, TI>;
+  if constexpr (KIND == kSPrevH || KIND == kSCurH) {
+    constexpr bool two = (KIND == kSPrevH ? sh_prev(I, TI, 1) : sh_cur(I, TI, 1)) >= 0;
+    ssegment_h<G, TI, FIRST, NRD, two>(a, b0, b1, acc, frag, [&](auto slot, auto unit) __attribute__((always_inline)) {
+      side(IC{}, SC{}, slot, unit);
+    }, hook);
+  } else {
+    ssegment<G, TI, FIRST, NRD, svpg<KIND>(I, TI)>(a, b0, b1, acc, [&]() __attribute__((always_inline)) {
+      static_for<4>(frag);
+    }, [&](auto ph) __attribute__((always_inline)) { side(IC{}, SC{}, ph); }, hook);
+  }
+}
+
 // One chunk-step: chunk c (global index, ring slot SLOT) = k-step i of group G; b0 / b1 its sample
 // tiles' operands.  On entry chunk c is published and tiles 0-2 of its fragments are in a[0..2].
 // TAIL = chunks left after c (capped at 3).
@@ -221,17 +358,14 @@ __device__ __forceinline__ void schunk(const float* __restrict__ stream, int c, 
   const float* cur = lds + SLOT * kChunkFloats;
   const float* nxt = lds + ((SLOT + 1) & 3) * kChunkFloats;
   auto none = [](auto) {};
-  auto sd = [&side](auto seg_c) __attribute__((always_inline)) {
-    return [&side, seg_c](auto ph) __attribute__((always_inline)) { side(std::integral_constant<int, I>{}, seg_c, ph); };
-  };
   using S0 = std::integral_constant<int, 0>;
   using S1 = std::integral_constant<int, 1>;
   using S2 = std::integral_constant<int, 2>;
   using S3 = std::integral_constant<int, 3>;
   // segment 0: this chunk's tile 3 fragments (their registers' last MFMAs were the previous chunk's)
-  ssegment<G, 0, FIRST, 1, svpg<KIND>(I, 0)>(a[0], b0, b1, acc, [&]() __attribute__((always_inline)) {
-    sread_tile<3>(cur, off, a[3]);
-  }, sd(S0{}), none);
+  sseg<G, 0, FIRST, 1, KIND, I>(a[0], b0, b1, acc, [&](auto kc) __attribute__((always_inline)) {
+    sread_frag<3, decltype(kc)::value>(cur, off, a[3]);
+  }, side, none);
   // publish chunk c+1: own DMA pieces landed (younger: chunk c+2's 4), barrier
   if constexpr (TAIL >= 1) {
     wait_vmcnt<TAIL >= 2 ? 4 : 0>();
@@ -242,23 +376,22 @@ __device__ __forceinline__ void schunk(const float* __restrict__ stream, int c, 
   // the barrier): pieces 0, 1 in segment 1, 2 and 3 in segments 2, 3, after a chain's MFMAs
   auto dma = [&](auto pc) __attribute__((always_inline)) {
     if constexpr (TAIL >= 3)
-      chunk_dma_piece<(SLOT + 3) & 3, decltype(pc)::value>(stream, WRAP ? (c + 3) & (kS16Chunks - 1) : c + 3, lds_dma,
-                                                           voff);
+      sdma_piece<(SLOT + 3) & 3, decltype(pc)::value>(stream, WRAP ? (c + 3) & (kS16Chunks - 1) : c + 3, lds_dma, voff);
   };
-  ssegment<G, 1, FIRST, (TAIL >= 1), svpg<KIND>(I, 1)>(a[1], b0, b1, acc, [&]() __attribute__((always_inline)) {
-    if constexpr (TAIL >= 1) sread_tile<0>(nxt, off, a[0]);
-  }, sd(S1{}), [&](auto jc) __attribute__((always_inline)) {
+  sseg<G, 1, FIRST, (TAIL >= 1), KIND, I>(a[1], b0, b1, acc, [&](auto kc) __attribute__((always_inline)) {
+    if constexpr (TAIL >= 1) sread_frag<0, decltype(kc)::value>(nxt, off, a[0]);
+  }, side, [&](auto jc) __attribute__((always_inline)) {
     if constexpr (decltype(jc)::value == 0) dma(S0{});
     if constexpr (decltype(jc)::value == 2) dma(S1{});
   });
-  ssegment<G, 2, FIRST, (TAIL >= 1), svpg<KIND>(I, 2)>(a[2], b0, b1, acc, [&]() __attribute__((always_inline)) {
-    if constexpr (TAIL >= 1) sread_tile<1>(nxt, off, a[1]);
-  }, sd(S2{}), [&](auto jc) __attribute__((always_inline)) {
+  sseg<G, 2, FIRST, (TAIL >= 1), KIND, I>(a[2], b0, b1, acc, [&](auto kc) __attribute__((always_inline)) {
+    if constexpr (TAIL >= 1) sread_frag<1, decltype(kc)::value>(nxt, off, a[1]);
+  }, side, [&](auto jc) __attribute__((always_inline)) {
     if constexpr (decltype(jc)::value == 0) dma(S2{});
   });
-  ssegment<G, 3, FIRST, (TAIL >= 1), svpg<KIND>(I, 3)>(a[3], b0, b1, acc, [&]() __attribute__((always_inline)) {
-    if constexpr (TAIL >= 1) sread_tile<2>(nxt, off, a[2]);
-  }, sd(S3{}), [&](auto jc) __attribute__((always_inline)) {
+  sseg<G, 3, FIRST, (TAIL >= 1), KIND, I>(a[3], b0, b1, acc, [&](auto kc) __attribute__((always_inline)) {
+    if constexpr (TAIL >= 1) sread_frag<2, decltype(kc)::value>(nxt, off, a[2]);
+  }, side, [&](auto jc) __attribute__((always_inline)) {
     if constexpr (decltype(jc)::value == 0) dma(S3{});
   });
 }
@@ -328,6 +461,75 @@ __device__ __forceinline__ void squarter(const SAcc& acc, const float (&inv)[2],
       op.lo[j + 1] = lo2[1];
     }
   }
+}
+
+// `v` made to depend on `after` (no instruction): two values the compiler sees as dependent are not
+// paired into one packed-f32 instruction.  Beside MFMAs a v_pk_fma_f32 or v_pk_mul_f32 costs more
+// than the two instructions it replaces (MI355X: +22 cycles per v_pk_fma_f32).  `v` is first read
+// an MFMA gap later: the compiler puts an s_nop between an asm statement and a reader of its output.
+__device__ __forceinline__ void sunpaired(float& v, float after) {
+#ifndef NERF16S_PACKED_SIDE   // (A/B build: the compiler's pairing)
+  asm("" : "+v"(v) : "v"(after));
+#endif
+}
+
+typedef float f32x2s __attribute__((ext_vector_type(2)));
+struct SHalf {
+  f32x2s b;
+  float y[2], xs[2];
+};
+
+// Half H (0..31) of the 4-tile group from tile T0: values 2p, 2p + 1 (p = H & 1) of quarter H >> 1,
+// squarter's arithmetic for them operation for operation (no density dot: the trunk's sides have
+// none), as units of at most two VALU instructions, one unit per MFMA gap (ssegment_h).  The second
+// value runs a unit behind the first, so that a gap's two instructions are of different kinds:
+//   -1 the bias read | 0 y0 = acc inv + b | 1 y1, ReLU y0 | 2 ReLU y1, x0 = y0 sc | 3 x1, maximum |
+//   4 the f16 hi pair | 5 the lo pair
+template <int U, int T0, int H>
+__device__ __forceinline__ void shalf(const SAcc& acc, const float (&inv)[2], const float* bias, int nlane,
+                                      const float (&sc)[2], Operand (&in)[16], float (&m)[2], SHalf& hv) {
+  constexpr int QG = H >> 1, p = H & 1, T = T0 + QG / 4, r = (QG % 4) >> 1, st = QG & 1, j = 4 * r + 2 * p;
+  typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+  Operand& op = in[2 * T + st];
+  if constexpr (U == -1) hv.b = *reinterpret_cast<const f32x2s*>(bias + 32 * T + 8 * r + nlane + 2 * p);
+  if constexpr (U == 0) {
+    hv.y[0] = fmaf(acc[T][r][st][2 * p], inv[st], hv.b[0]);
+    float b1 = hv.b[1];
+    sunpaired(b1, hv.y[0]);
+    hv.b[1] = b1;
+  }
+  if constexpr (U == 1) {
+    hv.y[1] = fmaf(acc[T][r][st][2 * p + 1], inv[st], hv.b[1]);
+    hv.y[0] = fmaxf(hv.y[0], 0.0f);
+  }
+  if constexpr (U == 2) {
+    hv.y[1] = fmaxf(hv.y[1], 0.0f);
+    hv.xs[0] = hv.y[0] * sc[st];
+    sunpaired(hv.y[1], hv.xs[0]);
+  }
+  if constexpr (U == 3) {
+    hv.xs[1] = hv.y[1] * sc[st];
+    m[st] = fmaxf(fmaxf(m[st], hv.y[0]), hv.y[1]);
+  }
+  if constexpr (U == 4) {
+    const h16x2 hi2 = {(_Float16)hv.xs[0], (_Float16)hv.xs[1]};
+    op.hi[j] = hi2[0];
+    op.hi[j + 1] = hi2[1];
+  }
+  if constexpr (U == 5) {
+    const h16x2 hi2 = {op.hi[j], op.hi[j + 1]};
+    const h16x2 lo2 = __builtin_bit_cast(h16x2, split_lo_pair(__builtin_bit_cast(uint32_t, hi2), hv.xs[0], hv.xs[1]));
+    op.lo[j] = lo2[0];
+    op.lo[j + 1] = lo2[1];
+  }
+}
+
+// A segment's second half runs a unit behind its first (unit U of the second just done, U + 1 of the
+// first before it): the second's scale products are kept from pairing with the first's.
+template <int U>
+__device__ __forceinline__ void shalf_follow(const SHalf& first, SHalf& second) {
+  if constexpr (U == 1) sunpaired(second.y[0], first.xs[0]);
+  if constexpr (U == 2) sunpaired(second.y[1], first.xs[1]);
 }
 
 // PE operand of k-step t, sample tile st, split at sc[st] from this wave's LDS copy: phase 0 reads the

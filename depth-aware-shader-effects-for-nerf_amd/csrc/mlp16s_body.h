@@ -96,7 +96,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_sched_barrier(0);
   const float* stream = packed + kOff16;
-  uint32_t lds_dma = (uint32_t)(uintptr_t)(lptr_t)lds + 1024u * wave;
+  uint32_t lds_dma = (uint32_t)(uintptr_t)(lptr_t)lds + kSDmaWave * wave;
   // fragment offsets: row half r, lane l reads piece (g >> 1) lane R_r(l & 15) + 32 (g & 1)
   auto fragment_offsets = [](int l, uint32_t (&off)[2]) __attribute__((always_inline)) {
     const int li = l & 15, hh = (l >> 4) & 1, ss = l >> 5;
@@ -117,10 +117,10 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   // theirs from the colour layer of the block before
   STile a[4];
   {
-    const uint32_t voff = 16u * lane0 + 1024u * wave;
-    chunk_dma<0>(stream, 0, lds_dma, voff);
-    chunk_dma<1>(stream, 1, lds_dma, voff);
-    chunk_dma<2>(stream, 2, lds_dma, voff);
+    const uint32_t voff = 16u * lane0 + kSDmaWave * wave;
+    sdma_chunk<0>(stream, 0, lds_dma, voff);
+    sdma_chunk<1>(stream, 1, lds_dma, voff);
+    sdma_chunk<2>(stream, 2, lds_dma, voff);
     uint32_t off[2];
     fragment_offsets(lane0, off);
     wait_vmcnt<8>();
@@ -146,7 +146,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   int lane = lane0;
   asm volatile("" : "+v"(lane));
   const int g = lane >> 4, li = lane & 15, hh = g & 1, ss = g >> 1;
-  const uint32_t voff = 16u * lane + 1024u * wave;
+  const uint32_t voff = 16u * lane + kSDmaWave * wave;
   uint32_t off[2];
   fragment_offsets(lane, off);
   const int nlane = 4 * hh + 16 * ss;   // this lane's neuron offset in a 16 x 16 output tile (+ 8r + e)
@@ -283,6 +283,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
     s_nxt[st] = pow2_scale(cst[kS16R + 0] * m_pe[st] + cst[kS16B + 0]);
   }
   SQuarter qv[2];
+  SHalf hv[2];
   float pe_v[8];
   auto pe_operand_of = [&](auto i, auto st) -> const Operand& {
     return pe_op[2 * decltype(i)::value + decltype(st)::value];
@@ -329,6 +330,27 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
       squarter<decltype(ph)::value, 0, q, decltype(sigma_tag)::value>(acc, inv_cur, bias_l, ws, nlane, s_nxt, in, m,
                                                                       part, qv[1]);
   };
+  // the plain trunk's sides in half-quarters, a unit per MFMA gap (ssegment_h; slot: the segment's
+  // first or second half)
+  auto side_prev_h = [&](auto i, auto seg, auto slot, auto unit) __attribute__((always_inline)) {
+    constexpr int h = sh_prev(decltype(i)::value, decltype(seg)::value, decltype(slot)::value);
+    if constexpr (h >= 0 && decltype(unit)::value >= -1)
+      shalf<decltype(unit)::value, 4, h>(acc, inv_prev, bias_prev, nlane, s_cur, in, m, hv[decltype(slot)::value]);
+    if constexpr (decltype(slot)::value == 1 && h >= 0)
+      shalf_follow<decltype(unit)::value>(hv[0], hv[1]);
+  };
+  auto side_cur_h = [&](auto i, auto seg, auto slot, auto unit, const float* bias_l) __attribute__((always_inline)) {
+    constexpr int h = sh_cur(decltype(i)::value, decltype(seg)::value, decltype(slot)::value);
+    if constexpr (h >= 0 && decltype(unit)::value >= -1)
+      shalf<decltype(unit)::value, 0, h>(acc, inv_cur, bias_l, nlane, s_nxt, in, m, hv[decltype(slot)::value]);
+    if constexpr (decltype(slot)::value == 1 && h >= 0)
+      shalf_follow<decltype(unit)::value>(hv[0], hv[1]);
+  };
+#ifdef NERF16S_QUARTER_SIDE   // (A/B build: the quarter schedule in the plain trunk too)
+  constexpr int kKindPrev = kSPrev, kKindCur = kSCur;
+#else
+  constexpr int kKindPrev = kSPrevH, kKindCur = kSCurH;
+#endif
   // the skip layer's PE operands at layer 4's input scale (s_cur in group A, which group B keeps)
   float s_pe[2] = {0.0f, 0.0f};
   auto side_pe = [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
@@ -359,10 +381,11 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
                                         side_pe(i, seg, ph);
                                       });
     } else {
-      sgroup<0, 8, 0, 3, kSPrev>(stream, c0, lds, lds_dma, voff, off, a, acc, act_operand,
-                                 [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
-                                   side_prev(i, seg, ph, NoSigma{});
-                                 }, pub_a);
+      sgroup<0, 8, 0, 3, kKindPrev>(stream, c0, lds, lds_dma, voff, off, a, acc, act_operand,
+                                    [&](auto i, auto seg, auto... at) __attribute__((always_inline)) {
+                                      if constexpr (sizeof...(at) == 2) side_prev_h(i, seg, at...);
+                                      else side_prev(i, seg, at..., NoSigma{});
+                                    }, pub_a);
     }
     // the inputs of layer L are known: the scale of layer L+1's inputs from the bound on y_L
 #pragma unroll
@@ -381,12 +404,17 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
                                      });
     } else {
       // (layer 7, SG: the next block's encoding in the free segments)
-      sgroup<1, 8, 0, 3, SG ? kSCurPe : kSCur>(
+      sgroup<1, 8, 0, 3, SG ? kSCurPe : kKindCur>(
           stream, c0 + 8, lds, lds_dma, voff, off, a, acc, act_operand,
-          [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
-            side_cur(i, seg, ph, bias_l, sg_tag);
-            if constexpr (SG)
-              side_pe_next(std::integral_constant<int, spe_next<true>(decltype(i)::value, decltype(seg)::value)>{}, ph);
+          [&](auto i, auto seg, auto... at) __attribute__((always_inline)) {
+            if constexpr (sizeof...(at) == 2) {
+              side_cur_h(i, seg, at..., bias_l);
+            } else {
+              side_cur(i, seg, at..., bias_l, sg_tag);
+              if constexpr (SG)
+                side_pe_next(std::integral_constant<int, spe_next<true>(decltype(i)::value, decltype(seg)::value)>{},
+                             at...);
+            }
           });
     }
 #pragma unroll

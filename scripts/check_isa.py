@@ -1,4 +1,5 @@
-"""Build-time guard of the M0 register in the LDS-DMA weight streams (csrc/mlp16.hip, csrc/train.hip).
+"""Build-time guard of the M0 register in the LDS-DMA weight streams (csrc/mlp16.hip, csrc/mlp16s.hip,
+csrc/train.hip).
 
 The streams issue `s_mov_b32 m0, <lds address>` + `global_load_lds_dwordx4` from inline asm and declare
 M0 clobbered; the compiler is never told the value must survive, so the kernels are only correct
@@ -10,6 +11,12 @@ translation unit) and checks, in every kernel whose name matches --kernels:
     by the LDS-DMA load that consumes it, or is the restore of a saved piece
     (`s_mov_b32 s<k>, m0; s_mov_b32 m0, s<n>; [s_nop]; <LDS-DMA>; s_mov_b32 m0, s<k>`: the per-ray
     feature-row DMA of mlp16.hip, which saves M0 instead of clobbering it);
+  * in the render kernels (HOLD_KERNELS: csrc/mlp16s.hip's own DMA), whose chunk pieces 1-3 reuse
+    the M0 that piece 0 wrote (one M0 write per chunk, the pieces told apart by the instruction's
+    immediate offset), an LDS-DMA load without an M0 write of its own is reached only with that M0
+    held: on the straight line from a piece that wrote it, with no M0 write other than a saved
+    piece's (which restores it), no branch, branch target, barrier or end of program in between
+    (check_held_m0).  Everywhere else such a load is a violation;
   * no other instruction names M0 as an operand or reads it implicitly (s_movrel*, v_movrel*,
     s_set_gpr_idx*, ds_*_addtid*, ds_gws_*, ds_append/ds_consume, ds_ordered_count, s_sendmsg*,
     v_interp*, and any LDS-DMA load that is not directly behind its own M0 write);
@@ -37,6 +44,7 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 DEFAULT_KERNELS = r"mlp16_kernel|mlp16s_kernel|mlp16s_live_kernel|mlp_backward16"
 DEFAULT_STREAMS = r"mlp16_kernel|mlp16s_kernel|mlp16s_live_kernel|mlp_backward16_bound"
+HOLD_KERNELS = r"mlp16s_kernel|mlp16s_live_kernel"
 IMPLICIT_M0 = re.compile(r"^(s_movrel|v_movrel|s_set_gpr_idx|ds_\w*addtid|ds_gws_|ds_append|ds_consume|"
                          r"ds_ordered_count|s_sendmsg|v_interp|s_ttracedata)")
 LDS_DMA = re.compile(r"^(global_load_lds_|buffer_load_\w+.*\blds\b|buffer_load_lds_)")
@@ -96,8 +104,9 @@ def functions(text):
     return funcs
 
 
-def check_function(insns):
-    """Violations in one kernel's instruction list, and its DMA-piece count."""
+def check_function(insns, hold=False):
+    """Violations in one kernel's instruction list, and its DMA-piece count.  hold: an LDS-DMA load
+    without an M0 write of its own is left to check_held_m0."""
     bad, pieces = [], 0
     pending = None                     # index of an M0 write waiting for its DMA
     real = [(i, ins) for i, ins in enumerate(insns) if ins.split()[0] != "s_nop"]
@@ -118,7 +127,7 @@ def check_function(insns):
                 continue
         j += 1
         if LDS_DMA.match(ins):
-            if pending is None:
+            if pending is None and not hold:
                 bad.append(f"{i}: LDS-DMA load not directly behind its own M0 write: {ins}")
             else:
                 pieces += 1
@@ -141,6 +150,40 @@ def check_function(insns):
     if pending is not None:
         bad.append(f"{pending}: M0 written at the end of the kernel without a DMA")
     return bad, pieces
+
+
+# ---- M0 held across a chunk's pieces ---------------------------------------------------------------
+def check_held_m0(insns):
+    """Violations of the held-M0 rule in one kernel ([(address, instruction, branch target)], as
+    _instructions gives): every LDS-DMA load that is not directly behind its own M0 write follows,
+    in a straight line, a piece that wrote M0."""
+    bad = []
+    targets = {tgt for _, _, tgt in insns if tgt is not None}
+    held, saved, own = False, None, False              # own: the previous instruction wrote M0 for a piece
+    for addr, ins, _ in insns:
+        op = ins.split()[0]
+        if op == "s_nop":
+            continue
+        if addr in targets:
+            held = False
+        save = re.match(r"^s_mov_b32\s+(s\d+)\s*,\s*m0\s*$", ins)
+        write = re.match(r"^s_mov_b32\s+m0\s*,\s*(s\d+)\s*$", ins)
+        wrote = False
+        if LDS_DMA.match(ins):
+            if own:
+                held = True
+            elif not held:
+                bad.append(f"{addr:x}: LDS-DMA load without an M0 write of its own where M0 is not held: {ins}")
+        elif save:
+            saved = (save.group(1), held)
+        elif write and saved is not None and write.group(1) == saved[0]:
+            held, saved = saved[1], None                 # a saved piece's restore
+        elif re.match(r"^\s*m0\s*,", ins[len(op):]):
+            held, wrote = False, write is not None       # (its own piece sets it again)
+        elif BRANCH.match(ins) or op in ("s_barrier", "s_endpgm") or op.startswith("s_setpc"):
+            held = False
+        own = wrote
+    return bad
 
 
 # ---- counted vmcnt waits of the LDS-DMA streams --------------------------------------------------
@@ -370,7 +413,10 @@ def check(text, kernels=DEFAULT_KERNELS, streams=DEFAULT_STREAMS):
         if not re.search(kernels, name):
             continue
         checked.append(name)
-        bad, pieces = check_function(insns)
+        hold = re.search(HOLD_KERNELS, name) is not None
+        bad, pieces = check_function(insns, hold)
+        if hold:
+            bad += check_held_m0(addressed.get(name, []))
         bad += check_store_data(insns)
         if pieces == 0 and re.search(streams, name):
             bad.append("no LDS-DMA piece found (the stream pattern changed: update this check)")
