@@ -127,6 +127,18 @@ _SIGNATURES = {
                                           ctypes.c_size_t, _V]),
     "nerf_train_backward": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _I64,
                                            ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V]),
+    # training with an occupancy grid (include/nerfmi_train.h)
+    "nerf_train_occ_workspace_bytes": (ctypes.c_size_t, [_I64, ctypes.c_int]),
+    "nerf_train_occ_sample": (ctypes.c_int, [_V, _V, _I64, ctypes.c_double, ctypes.c_double, ctypes.c_int, _V,
+                                             ctypes.c_int, _V, ctypes.c_uint64, _V, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _V, _V,
+                                             ctypes.c_size_t, _V]),
+    "nerf_train_occ_forward": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, _I64, _V, _I64, _V, _V, _V, _V, _V,
+                                              ctypes.c_size_t, _V]),
+    "nerf_train_occ_backward": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _I64, _V, _I64,
+                                               ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V]),
+    "nerf_mlp_forward_train_live": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V, _I64, _V, _V, _V,
+                                                   _V, _V, _V, _V]),
     # depth-aware post effects (include/nerfmi.h)
     "nerf_effect_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "nerf_depth_normalize": (ctypes.c_int, [_V, _I64, _V, _V, ctypes.c_size_t, _V]),

@@ -157,6 +157,10 @@ extern int g_mlp_arith;   // nerf_arith, set by nerf_set_mlp_arith
 int launch_mlp16(const float* packed, const float* o, const float* d, const float* z, int64_t R, int N,
                  const float* feat, float* rgb, float* sigma, const int* out_slot, int out_T, hipStream_t s,
                  float* save = nullptr, const float* encd = nullptr, uint32_t* masks = nullptr);
+// the training forward on the M_live samples a live list names, writing compact rows (mlp16.hip)
+int launch_mlp16_live(const float* packed, const float* o, const float* d, const float* z, int N, const float* feat,
+                      const float* encd, const int* live, int64_t M_live, float* rgb, float* sigma, float* rgb_live,
+                      float* sigma_live, float* save, uint32_t* masks, hipStream_t s);
 // the render MLP on 16 x 16 x 32 tiles (mlp16s.hip): launch_mlp16 without saves
 int launch_mlp16s(const float* packed, const float* o, const float* d, const float* z, int64_t R, int N,
                   const float* feat, float* rgb, float* sigma, const int* out_slot, int out_T, hipStream_t s);
@@ -170,6 +174,9 @@ size_t occ_block_count_bytes(int64_t M);
 int launch_occ_classify(const float* o, const float* d, const float* z, int64_t B, int n, const uint32_t* bits, int G,
                         const float* lo, const float* inv, int* live, int* live_count, uint8_t* mask,
                         float* sigma_zero, float* rgb_zero, uint32_t* block_counts, hipStream_t s);
+// dsigma_live[i] = dsigma[live[i]], drgb_live[i] = drgb[live[i]] for i < M_live (training with a grid)
+int launch_occ_gather_grads(const float* dsigma, const float* drgb, const int* live, int64_t M_live,
+                            float* dsigma_live, float* drgb_live, hipStream_t s);
 int launch_occ_pack(const float* lattice, int G, int sp, float thr, uint32_t* bits, hipStream_t s);
 int launch_occ_dilate(const uint32_t* in, int G, uint32_t* out, hipStream_t s);
 int launch_mlp(const float* packed, const float* o, const float* d, const float* z, int64_t R,

@@ -153,6 +153,30 @@ int launch_occ_classify(const float* o, const float* d, const float* z, int64_t 
   return check_launch("occ_write_kernel");
 }
 
+// Training with a grid (train.hip, nerf_train_occ_backward): the composite backward runs dense on
+// (B, N); the rows of its dsigma / drgb that the live list names are gathered into the compact rows
+// the MLP backward reads.  What it formed at dead rows is dropped (sigma = 0 there is a constant).
+__global__ void __launch_bounds__(256) occ_gather_grads_kernel(const float* __restrict__ dsigma,
+                                                               const float* __restrict__ drgb,
+                                                               const int* __restrict__ live, int64_t M_live,
+                                                               float* __restrict__ dsigma_live,
+                                                               float* __restrict__ drgb_live) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M_live) return;
+  const int64_t s = live[i];
+  dsigma_live[i] = dsigma[s];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) drgb_live[3 * i + c] = drgb[3 * s + c];
+}
+
+int launch_occ_gather_grads(const float* dsigma, const float* drgb, const int* live, int64_t M_live,
+                            float* dsigma_live, float* drgb_live, hipStream_t s) {
+  if (M_live == 0) return NERF_OK;
+  hipLaunchKernelGGL(occ_gather_grads_kernel, dim3((unsigned)((M_live + 255) / 256)), dim3(256), 0, s, dsigma, drgb,
+                     live, M_live, dsigma_live, drgb_live);
+  return check_launch("occ_gather_grads_kernel");
+}
+
 // ------------------------------------------------------------------------- grid construction
 // bit of cell (ix, iy, iz) = any of its s^3 probes of the (sG)^3 lattice (index (z sG + y) sG + x)
 // is > threshold (the max over the probes, NaN probes ignored as fmaxf does).  A wave's ballot is two

@@ -3272,4 +3272,208 @@ int nerf_train_backward(const float* packed, const float* packedT, const float* 
   return param_grads(R(T_SAVE), R(T_GRAD), M, N, app, app_rows, packed, param_grads_out, dapp, R(T_WG), wg_floats, s);
 }
 
+// ------------------------------------------------------- the training step with an occupancy grid
+// (include/nerfmi_train.h "training with an occupancy grid").  Three calls, because the
+// library never synchronises and the live count has to reach the host once: sample (normalise, draw
+// z, classify into the ascending live list; dead rows of sigma / rgb zero-filled), forward (ray
+// features, the gathered forward writing COMPACT save / mask rows, the dense composite) and backward
+// (dense composite backward + loss, gather of dsigma / drgb, the per-row MLP backward and weight
+// gradients over M_live rows: the N = 1 route of param_grads, enc_d in every save row).
+//
+// Workspace: train_carve(B, N) (save / masks / grad hold the M_live <= B N compact rows; rgb, sigma,
+// dsigma, drgb stay dense), then, each 256-B aligned: the live list (B N int32), the classify block
+// counts, and the compact sigma (M), rgb (3M), dsigma (M), drgb (3M).  The count lives in the
+// caller's live_count.
+enum { TO_LIVE, TO_BLOCKS, TO_SIG, TO_RGB, TO_DSIG, TO_DRGB, TO_COUNT };
+static size_t train_occ_carve(int64_t B, int N, size_t* off, size_t* off_occ) {
+  size_t at = train_carve(B, N, off);
+  const size_t M = (size_t)B * (size_t)N;
+  const size_t sizes[TO_COUNT] = {M * 4, occ_block_count_bytes((int64_t)M), M * 4, M * 12, M * 4, M * 12};
+  for (int i = 0; i < TO_COUNT; ++i) {
+    off_occ[i] = at;
+    at += align256(sizes[i]);
+  }
+  return at;
+}
+constexpr int64_t kOccMaxSamples = (int64_t)1 << 30;   // the live list's int32 indices (occupancy.hip)
+constexpr int kFwdOcc = -2;                            // forward_arith of a workspace an occ forward wrote
+// M_live of the last nerf_train_occ_forward on a workspace (host-side, as g_ws_arith)
+static std::unordered_map<const void*, int64_t> g_ws_occ_live;
+static void remember_occ_forward(const void* ws, int64_t M_live) {
+  remember_forward_arith(ws, kFwdOcc);      // nerf_train_backward refuses this workspace (< 0)
+  std::lock_guard<std::mutex> lk(g_ws_mu);
+  if (g_ws_occ_live.size() > 4096) g_ws_occ_live.clear();
+  g_ws_occ_live[ws] = M_live;
+}
+static int64_t occ_forward_live(const void* ws) {
+  if (forward_arith(ws) != kFwdOcc) return -1;
+  std::lock_guard<std::mutex> lk(g_ws_mu);
+  const auto it = g_ws_occ_live.find(ws);
+  return it == g_ws_occ_live.end() ? -1 : it->second;
+}
+// floats of state_dict tensor p (nerf_pack_weights order)
+static size_t param_floats(int p) {
+  if (p < 16) {
+    const int L = p / 2;
+    if (p % 2) return kHidden;
+    return (size_t)kHidden * (L == 0 ? kPosEnc : L == kSkipLayer ? kHidden + kPosEnc : kHidden);
+  }
+  switch (p) {
+    case P_SIGMA_W: return kHidden;
+    case P_SIGMA_B: return 1;
+    case P_DIR_W: return (size_t)kDirHidden * (kHidden + kDirEnc);
+    case P_DIR_B: return kDirHidden;
+    case P_APP_W: return (size_t)kDirHidden * kAppDim;
+    case P_APP_B: return kDirHidden;
+    case P_RGB_W: return 3 * kDirHidden;
+    default: return 3;
+  }
+}
+
+#define TREQUIRE_SHAPE(fn, B, N)                                                                              \
+  do {                                                                                                        \
+    TREQUIRE((B) >= 0, fn ": B=%lld", (long long)(B));                                                        \
+    if ((N) < 1 || (N) > 4096) return set_error(NERF_ERR_UNSUPPORTED, fn ": N=%d (1..4096)", (N));            \
+    if ((int64_t)(B) * (N) > kOccMaxSamples)                                                                  \
+      return set_error(NERF_ERR_UNSUPPORTED, fn ": %lld samples exceed the limit %lld", (long long)(B) * (N), \
+                       (long long)kOccMaxSamples);                                                            \
+  } while (0)
+
+size_t nerf_train_occ_workspace_bytes(int64_t B, int N) {
+  if (B < 0 || N < 1 || N > 4096 || B * (int64_t)N > kOccMaxSamples) return 0;
+  size_t off[T_COUNT], off_occ[TO_COUNT];
+  return train_occ_carve(B, N, off, off_occ);
+}
+
+int nerf_train_occ_sample(const float* rays_o, const float* rays_d, int64_t B, double near, double far, int N,
+                          const float* t_vals, int perturb, const float* t_rand, uint64_t seed, const uint32_t* bits,
+                          int G, const float* lo, const float* inv, int32_t* live_count, void* workspace,
+                          size_t ws_bytes, nerf_stream_t stream) {
+  TREQUIRE_SHAPE("nerf_train_occ_sample", B, N);
+  TREQUIRE(bits && lo && inv && live_count, "nerf_train_occ_sample: null pointer");
+  TREQUIRE(B == 0 || (rays_o && rays_d && t_vals && workspace), "nerf_train_occ_sample: null pointer");
+  if (G < 1 || G > 1024) return set_error(NERF_ERR_UNSUPPORTED, "nerf_train_occ_sample: G=%d outside 1..1024", G);
+  size_t off[T_COUNT], off_occ[TO_COUNT];
+  const size_t need = train_occ_carve(B, N, off, off_occ);
+  if (B > 0 && ws_bytes < need)
+    return set_error(NERF_ERR_WORKSPACE, "nerf_train_occ_sample: workspace %zu < %zu bytes", ws_bytes, need);
+  char* ws = (char*)workspace;
+  auto R = [&](int i) { return (float*)(ws + off[i]); };
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = launch_normalize(rays_d, B, R(T_DIRS), s))) return rc;                                       // render.py:19
+  if ((rc = launch_stratified(rays_o, R(T_DIRS), B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand,
+                              seed, R(T_Z), nullptr, s)))
+    return rc;
+  return launch_occ_classify(rays_o, R(T_DIRS), R(T_Z), B, N, bits, G, lo, inv, (int*)(ws + off_occ[TO_LIVE]),
+                             live_count, nullptr, R(T_SIG), R(T_RGB), (uint32_t*)(ws + off_occ[TO_BLOCKS]), s);
+}
+
+int nerf_train_occ_forward(const float* packed, const float* rays_o, int64_t B, int N, int64_t M_live,
+                           const float* app, int64_t app_rows, float* rgb_map, float* depth_map, float* weights_out,
+                           float* z_out, void* workspace, size_t ws_bytes, nerf_stream_t stream) {
+  TREQUIRE_SHAPE("nerf_train_occ_forward", B, N);
+  TREQUIRE(M_live >= 0 && M_live <= B * (int64_t)N, "nerf_train_occ_forward: M_live=%lld with B*N=%lld",
+           (long long)M_live, (long long)(B * (int64_t)N));
+  TREQUIRE(app_rows >= 0, "nerf_train_occ_forward: app_rows=%lld", (long long)app_rows);
+  if (app_rows > 1)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_train_occ_forward: app_rows=%lld (0 or 1: no per-ray appearance rows)",
+                     (long long)app_rows);
+  if (g_mlp_arith != NERF_ARITH_F16X3)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_train_occ_forward: the gathered training forward is f16x3 only");
+  if (B == 0) return NERF_OK;
+  TREQUIRE(packed && rays_o && rgb_map && depth_map && workspace && (app_rows == 0 || app),
+           "nerf_train_occ_forward: null pointer");
+  size_t off[T_COUNT], off_occ[TO_COUNT];
+  const size_t need = train_occ_carve(B, N, off, off_occ);
+  if (ws_bytes < need)
+    return set_error(NERF_ERR_WORKSPACE, "nerf_train_occ_forward: workspace %zu < %zu bytes", ws_bytes, need);
+  char* ws = (char*)workspace;
+  auto R = [&](int i) { return (float*)(ws + off[i]); };
+  auto RO = [&](int i) { return (float*)(ws + off_occ[i]); };
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  // T_DIRS holds the normalised directions (nerf_train_occ_sample): the features from them as they are
+  if ((rc = launch_ray_features(packed, R(T_DIRS), B, app, app_rows, R(T_FEAT), s, R(T_ENCD), nullptr))) return rc;
+  if ((rc = launch_mlp16_live(packed, rays_o, R(T_DIRS), R(T_Z), N, R(T_FEAT), R(T_ENCD), (const int*)RO(TO_LIVE),
+                              M_live, R(T_RGB), R(T_SIG), RO(TO_RGB), RO(TO_SIG), R(T_SAVE), (uint32_t*)R(T_MASK), s)))
+    return rc;
+  remember_occ_forward(workspace, M_live);
+  if ((rc = launch_composite(R(T_RGB), R(T_SIG), R(T_Z), B, N, rgb_map, depth_map, weights_out, s))) return rc;
+  if (z_out && hipMemcpyAsync(z_out, R(T_Z), (size_t)B * N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "nerf_train_occ_forward: z copy failed");
+  return NERF_OK;
+}
+
+int nerf_train_occ_backward(const float* packed, const float* packedT, const float* rgb_map, const float* target,
+                            int64_t B, int N, int64_t M_live, const float* app, int64_t app_rows,
+                            float* const* param_grads_out, float* dapp, float* loss, void* workspace, size_t ws_bytes,
+                            nerf_stream_t stream) {
+  TREQUIRE_SHAPE("nerf_train_occ_backward", B, N);
+  TREQUIRE(M_live >= 0 && M_live <= B * (int64_t)N, "nerf_train_occ_backward: M_live=%lld with B*N=%lld",
+           (long long)M_live, (long long)(B * (int64_t)N));
+  TREQUIRE(app_rows >= 0, "nerf_train_occ_backward: app_rows=%lld", (long long)app_rows);
+  if (app_rows > 1)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_train_occ_backward: app_rows=%lld (0 or 1: no per-ray appearance rows)",
+                     (long long)app_rows);
+  if (g_mlp_arith != NERF_ARITH_F16X3)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_train_occ_backward: the gathered training step is f16x3 only");
+  TREQUIRE(packed && packedT && param_grads_out && loss && workspace && (B == 0 || (rgb_map && target)) &&
+               (app_rows == 0 || app),
+           "nerf_train_occ_backward: null pointer");
+  for (int i = 0; i < P_COUNT; ++i) TREQUIRE(param_grads_out[i], "nerf_train_occ_backward: gradient %d is null", i);
+  if (B == 0) return NERF_OK;
+  size_t off[T_COUNT], off_occ[TO_COUNT];
+  const size_t need = train_occ_carve(B, N, off, off_occ);
+  if (ws_bytes < need)
+    return set_error(NERF_ERR_WORKSPACE, "nerf_train_occ_backward: workspace %zu < %zu bytes", ws_bytes, need);
+  if (occ_forward_live(workspace) != M_live)
+    return set_error(NERF_ERR_BAD_ARG, "nerf_train_occ_backward: no nerf_train_occ_forward with M_live=%lld wrote this "
+                     "workspace", (long long)M_live);
+  char* ws = (char*)workspace;
+  auto R = [&](int i) { return (float*)(ws + off[i]); };
+  auto RO = [&](int i) { return (float*)(ws + off_occ[i]); };
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  const float scale = (float)(2.0 / (3.0 * (double)B));                                              // train.py:87
+  if ((rc = launch_composite_backward(R(T_RGB), R(T_SIG), R(T_Z), rgb_map, target, nullptr, nullptr, B, N, scale,
+                                      R(T_DSIG), R(T_DRGB), R(T_SQE), s)))
+    return rc;
+  hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, s, R(T_SQE), B, loss);
+  if ((rc = check_launch("loss_kernel"))) return rc;
+  if (M_live == 0) {   // every sample dead: sigma = 0 is a constant of the step, every gradient is zero
+    for (int p = 0; p < P_COUNT; ++p)
+      if (hipMemsetAsync(param_grads_out[p], 0, param_floats(p) * 4, s) != hipSuccess)
+        return set_error(NERF_ERR_HIP, "nerf_train_occ_backward: hipMemsetAsync failed");
+    if (dapp && app_rows && hipMemsetAsync(dapp, 0, (size_t)kAppDim * 4, s) != hipSuccess)
+      return set_error(NERF_ERR_HIP, "nerf_train_occ_backward: hipMemsetAsync failed");
+    return NERF_OK;
+  }
+  if ((rc = launch_occ_gather_grads(R(T_DSIG), R(T_DRGB), (const int*)RO(TO_LIVE), M_live, RO(TO_DSIG), RO(TO_DRGB),
+                                    s)))
+    return rc;
+  if ((rc = launch_mlp_backward(packed, packedT, R(T_SAVE), (const uint32_t*)R(T_MASK), RO(TO_SIG), RO(TO_RGB),
+                                RO(TO_DSIG), RO(TO_DRGB), M_live, R(T_GRAD), s, /*store_dhd=*/true)))
+    return rc;
+  const size_t wg_floats = (off_occ[0] - off[T_WG]) / 4;
+  return param_grads(R(T_SAVE), R(T_GRAD), M_live, 1, app, app_rows, packed, param_grads_out, dapp, R(T_WG),
+                     wg_floats, s);
+}
+
+int nerf_mlp_forward_train_live(const float* packed, const float* origins, const float* dirs, const float* z_vals,
+                                int64_t R, int N, const float* ray_feat, const float* enc_d, const int32_t* live,
+                                int64_t M_live, float* rgb, float* sigma, float* rgb_live, float* sigma_live,
+                                float* save, uint32_t* masks, nerf_stream_t stream) {
+  TREQUIRE_SHAPE("nerf_mlp_forward_train_live", R, N);
+  TREQUIRE(M_live >= 0 && M_live <= R * (int64_t)N, "nerf_mlp_forward_train_live: M_live=%lld with R*N=%lld",
+           (long long)M_live, (long long)(R * (int64_t)N));
+  TREQUIRE(M_live == 0 || (packed && origins && dirs && z_vals && ray_feat && enc_d && live && rgb && sigma &&
+                           rgb_live && sigma_live && save && masks),
+           "nerf_mlp_forward_train_live: null pointer");
+  if (g_mlp_arith != NERF_ARITH_F16X3)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_mlp_forward_train_live: the gathered kernel is f16x3 only");
+  return launch_mlp16_live(packed, origins, dirs, z_vals, N, ray_feat, enc_d, live, M_live, rgb, sigma, rgb_live,
+                           sigma_live, save, masks, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -11,6 +11,10 @@ Cell (ix, iy, iz) is bit ``index & 31`` of word ``index >> 5``, index = (iz*G + 
 at p = o + d*z is live iff for every axis t = (p - lo) * inv (float32, two roundings) has
 0 <= t < G and the bit of cell (int(t_x), int(t_y), int(t_z)) is set; rendering with a grid is the
 plain render with the sigma of every dead sample replaced by 0 (the MLP is not run on them).
+Training takes the same grid and the same rule (train.py: ``Trainer(config, occupancy=grid,
+occupancy_refresh={...})``, ``train_nerf(..., occupancy=grid)``): a step runs the MLP
+forward, backward and weight gradients on the live samples only, and with ``occupancy_refresh`` the
+trainer rebuilds the bits from its own model (from_model) as the weights change.
 
 Builders (each returns the grid):
   grid.from_mask(mask)           bool (G,G,G) indexed [iz, iy, ix]

@@ -24,8 +24,10 @@ and ``background_color``.  Keyword-only extras:
                       coarse samples in the fine pass — bit-identical, for the tests.
   occupancy           an OccupancyGrid (occupancy.py; not a reference feature): the sigma of every
                       sample outside the grid's set cells is 0 and the MLP is not run on it
-                      (nerf_render_rays_occ).  Inference only, single-call path only: combined with
-                      gradients, staged=True or timing= it raises ValueError.
+                      (nerf_render_rays_occ).  volume_render takes a grid on the single-call
+                      inference path only: combined with gradients, staged=True or timing= it raises
+                      ValueError.  Training with a grid is the Trainer's (train.py,
+                      Trainer(occupancy=)), not autograd's.
 ``render_rays`` is the same function (the north-star name).
 
 With gradients enabled and a trainable model (or an appearance embedding that requires grad),
@@ -70,9 +72,9 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
         grad = autograd.needs_grad(model, appearance_embedding if uses_appearance(model) else None, rays_o, rays_d)
         if grad or staged or timing is not None:
             what = "gradients enabled" if grad else ("staged=True" if staged else "timing=")
-            raise ValueError(f"nerfmi.volume_render(occupancy=) with {what}: sample skipping is an inference "
-                             f"feature of the single-call path (render under torch.no_grad(), without staged / "
-                             f"timing)")
+            raise ValueError(f"nerfmi.volume_render(occupancy=) with {what}: volume_render skips samples on the "
+                             f"single-call inference path only (render under torch.no_grad(), without staged / "
+                             f"timing; to train with a grid use nerfmi.train.Trainer(occupancy=))")
     if autograd.needs_grad(model, appearance_embedding if uses_appearance(model) else None, rays_o, rays_d):
         if hierarchical or staged or timing is not None:
             what = "hierarchical=True" if hierarchical else ("staged=True" if staged else "timing=")

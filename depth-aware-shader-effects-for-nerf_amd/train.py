@@ -39,10 +39,26 @@ class Trainer:
     """Flat-buffer NeRF (+ appearance table) trainer: one object per rank.
 
     ``group``: a torch.distributed process group for data parallelism (gradients averaged over
-    it before the optimizer step, as DDP would); None trains on this process alone."""
+    it before the optimizer step, as DDP would); None trains on this process alone.
+
+    ``occupancy``: an OccupancyGrid on this process's device.  Every step then classifies its
+    samples against the grid and runs the MLP forward, backward and weight gradients on the live
+    ones only (include/nerfmi_train.h "training with an occupancy grid"): a dead
+    sample has sigma = 0 as a constant of the step.  f16x3 arithmetic only.  The step costs one host
+    wait (the live count), placed behind the weight packings.
+
+    ``occupancy_refresh``: None keeps the grid's bits as given.  A dict (missing keys take
+    OCCUPANCY_REFRESH_DEFAULTS) makes the trainer keep the grid current while the model changes: for
+    the first ``warmup`` optimizer steps the grid is all ones over its box, and after optimizer
+    step k >= warmup with k == warmup or k % every == 0 the bits are replaced by
+    OccupancyGrid.from_model(self.model, box, resolution, threshold, supersample, dilate).  The
+    rebuild is deterministic, so data-parallel ranks (identical weights) rebuild identical bits and
+    nothing is communicated."""
 
     def __init__(self, config, model=None, appearance_embeddings=None, n_images=None, group=None,
-                 lr=None, betas=(0.9, 0.999), eps=1e-8, near=None, far=None):
+                 lr=None, betas=(0.9, 0.999), eps=1e-8, near=None, far=None, occupancy=None,
+                 occupancy_refresh=None):
+        _check_occupancy_args(occupancy, occupancy_refresh)
         self.config = config
         # the sampling interval: the dataset's near/far (train.py:79 passes dataset.near/far), the
         # config's when no dataset is given
@@ -114,6 +130,23 @@ class Trainer:
         self._ws = None
         self._tvals = {}
         self._side = None          # side stream for the transposed packing (forward_backward)
+        self.occupancy = occupancy
+        self.occupancy_refresh = None
+        self.live_fraction = None  # share of the last step's samples the grid marked live
+        if occupancy is not None:
+            if occupancy.device != self.dev:
+                raise ValueError(f"Trainer: the occupancy grid is on {occupancy.device}, the trainer on {self.dev}")
+            if occupancy_refresh is not None:
+                self.occupancy_refresh = dict(OCCUPANCY_REFRESH_DEFAULTS, **occupancy_refresh)
+                if self.occupancy_refresh["warmup"] > 0:
+                    G = occupancy.resolution
+                    occupancy.from_mask(torch.ones(G, G, G, dtype=torch.bool))
+                else:
+                    self._rebuild_occupancy()
+            self._live_dev = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            self._live_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self._live_ev = torch.cuda.Event()
+            self._ws_occ = None
 
     def view(self, buf, i):
         return buf[self.offsets[i]: self.offsets[i + 1]].view(self.shapes[i])
@@ -140,6 +173,8 @@ class Trainer:
             assert t_rand.shape == (B, N)
         if seed is None:
             seed = step_seed(self.steps + 1, self.rank)
+        if self.occupancy is not None:
+            return self._forward_backward_occ(o, d, tgt, app_idx, t_rand, seed, _marks)
         _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
         # The transposed weights are read only by the backward: they are packed on a side stream while
         # the forward runs (forked after everything queued so far, so after the previous step's
@@ -181,6 +216,74 @@ class Trainer:
             self.view(self.grad, 20).zero_()
             self.view(self.grad, 21).zero_()
         return self.loss_buf[0], rgb_map
+
+    def _forward_backward_occ(self, o, d, tgt, app_idx, t_rand, seed, _marks=None):
+        """forward_backward on the live samples of self.occupancy: sample + classify, the live count
+        to pinned host memory behind an event, the two weight packings (which cover that copy), the
+        wait, then the gathered forward and the compact backward."""
+        lib, s, P = self.lib, _lib.stream(), _lib.ptr
+        g = self.occupancy
+        if _lib.get_mlp_arith() != "f16x3":
+            raise ValueError("Trainer: training with an occupancy grid runs under the f16x3 arithmetic only")
+        if g.device != self.dev:
+            raise ValueError(f"Trainer: the occupancy grid is on {g.device}, the trainer on {self.dev}")
+        N = self.config.num_samples
+        B = o.shape[0]
+        if N not in self._tvals:
+            self._tvals[N] = linspace_table(N, self.dev)
+        need = lib.nerf_train_occ_workspace_bytes(B, N)
+        if self._ws_occ is None or self._ws_occ.numel() < need:
+            self._ws_occ = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        ws = self._ws_occ
+        main = torch.cuda.current_stream(self.dev)
+        _lib.check(lib.nerf_train_occ_sample(P(o), P(d), B, self.near, self.far, N, P(self._tvals[N]), 1, P(t_rand),
+                                             int(seed), P(g.bits), g.resolution, g.c_lo(), g.c_inv(),
+                                             P(self._live_dev), P(ws), ws.numel(), s), "nerf_train_occ_sample")
+        self._live_host.copy_(self._live_dev, non_blocking=True)
+        self._live_ev.record(main)
+        _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.dev)
+            self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
+        self._fork.record(main)
+        self._side.wait_event(self._fork)
+        _lib.check(lib.nerf_pack_weights_transposed(self.param_ptrs, P(self.packedT), self._side.cuda_stream),
+                   "nerf_pack_weights_transposed")
+        if self.app_grad is not None:
+            with torch.cuda.stream(self._side):
+                self.app_grad.zero_()
+        self._join.record(self._side)
+        rgb_map = torch.empty(B, 3, device=self.dev)
+        depth = torch.empty(B, device=self.dev)
+        if self.n_images and app_idx is not None:
+            app, rows = self.appearance_embeddings[int(app_idx)].reshape(1, _APP_DIM), 1
+        else:
+            app, rows = None, 0
+        self._live_ev.synchronize()                      # the step's one host wait
+        m_live = int(self._live_host[0])
+        self.live_fraction = m_live / max(1, B * N)
+        if _marks is not None and len(_marks) > 5:       # (scripts/bench_train_occupancy.py: end of sample + wait)
+            _marks[5].record(main)
+        _lib.check(lib.nerf_train_occ_forward(P(self.packed), P(o), B, N, m_live, P(app), rows, P(rgb_map), P(depth),
+                                              None, None, P(ws), ws.numel(), s), "nerf_train_occ_forward")
+        if _marks is not None:
+            _marks[1].record(main)
+        dapp = self.app_grad[int(app_idx)] if rows else None
+        main.wait_event(self._join)
+        _lib.check(lib.nerf_train_occ_backward(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, m_live,
+                                               P(app), rows, self.grad_ptrs, P(dapp), P(self.loss_buf), P(ws),
+                                               ws.numel(), s), "nerf_train_occ_backward")
+        if rows == 0:
+            self.view(self.grad, 20).zero_()
+            self.view(self.grad, 21).zero_()
+        return self.loss_buf[0], rgb_map
+
+    def _rebuild_occupancy(self):
+        from .occupancy import OccupancyGrid
+        g, r = self.occupancy, self.occupancy_refresh
+        new = OccupancyGrid.from_model(self.model, g.lo, g.hi, resolution=g.resolution, threshold=r["threshold"],
+                                       supersample=r["supersample"], dilate=r["dilate"])
+        g.bits = new.bits
 
     def profile_step(self, rays_o, rays_d, target, app_idx=None, seed=12345):
         """Event-timed phases of one training step through the stage entry points (no parameter
@@ -254,6 +357,9 @@ class Trainer:
                                       float(self.betas[0]), float(self.betas[1]), float(self.eps), self.steps,
                                       _lib.stream()), "nerf_adam")
         self.model._packed = None          # the module's cached inference packing is stale now
+        r = self.occupancy_refresh
+        if r is not None and self.steps >= r["warmup"] and (self.steps == r["warmup"] or self.steps % r["every"] == 0):
+            self._rebuild_occupancy()
 
     def step(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, seed=None):
         loss, rgb = self.forward_backward(rays_o, rays_d, target, app_idx, t_rand=t_rand, seed=seed)
@@ -297,7 +403,34 @@ class Trainer:
               "iteration": iteration}
         if self.n_images:
             ck["appearance_embeddings"] = self.appearance_embeddings.detach().cpu().clone()
+        if self.occupancy is not None:
+            ck["occupancy"] = self.occupancy.state_dict()
         return ck
+
+
+# occupancy_refresh defaults (hyper-parameters, not gates): all ones for the first 256 steps, then a
+# rebuild every 256 steps at one probe per cell, sigma > 0.01, one dilation
+OCCUPANCY_REFRESH_DEFAULTS = {"every": 256, "warmup": 256, "threshold": 0.01, "dilate": 1, "supersample": 1}
+
+
+def _check_occupancy_args(occupancy, occupancy_refresh):
+    """ValueError for anything but an OccupancyGrid / a dict of the refresh keys (no device needed)."""
+    from .occupancy import OccupancyGrid
+    if occupancy is None:
+        if occupancy_refresh is not None:
+            raise ValueError("Trainer: occupancy_refresh needs an occupancy grid")
+        return
+    if not isinstance(occupancy, OccupancyGrid):
+        raise ValueError(f"Trainer: occupancy must be an OccupancyGrid, got {type(occupancy).__name__}")
+    if occupancy_refresh is None:
+        return
+    if not isinstance(occupancy_refresh, dict) or set(occupancy_refresh) - set(OCCUPANCY_REFRESH_DEFAULTS):
+        raise ValueError(f"Trainer: occupancy_refresh must be a dict with keys among "
+                         f"{sorted(OCCUPANCY_REFRESH_DEFAULTS)}, got {occupancy_refresh!r}")
+    r = dict(OCCUPANCY_REFRESH_DEFAULTS, **occupancy_refresh)
+    if int(r["every"]) < 1 or int(r["warmup"]) < 0 or int(r["dilate"]) < 0 or int(r["supersample"]) < 1:
+        raise ValueError(f"Trainer: occupancy_refresh={occupancy_refresh!r}: every >= 1, warmup >= 0, dilate >= 0, "
+                         f"supersample >= 1")
 
 
 def step_seed(key, rank):
@@ -331,7 +464,8 @@ def average_gradients(flat_grad, group):
 
 
 def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iterations=None, log_every=10,
-               checkpoint_every=1000, seed=None, plots=True, return_metrics=False):
+               checkpoint_every=1000, seed=None, plots=True, return_metrics=False, occupancy=None,
+               occupancy_refresh=None):
     """src/train.py:13-207 on nerfmi: returns the trained model, as the reference does
     (train.py:207; run.py:347 assigns it).  ``return_metrics=True`` returns (model, losses, psnrs)
     instead; the per-iteration losses and PSNRs are also left on ``train_nerf.losses`` /
@@ -339,15 +473,18 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
     trained in place (train.py:36-39).  Every ``checkpoint_every`` iterations rank 0 writes
     checkpoint_{i:06d}.pt and the validation render render_{i:06d}.png of train.py:127-173.
     Under data parallelism every rank draws its own batch (its own image, its own jitter
-    stream) and the gradients are averaged; rank 0 writes."""
+    stream) and the gradients are averaged; rank 0 writes.  ``occupancy`` / ``occupancy_refresh``
+    go to the Trainer (training on the live samples of an occupancy grid); the final and periodic
+    checkpoints then carry the grid's state_dict under "occupancy"."""
     import torch.distributed as dist
+    _check_occupancy_args(occupancy, occupancy_refresh)
     rank = dist.get_rank(group) if group is not None else 0
     if rank == 0:
         os.makedirs(save_dir, exist_ok=True)
     initial_batch_size = min(64, config.batch_size)                    # train.py:26
     trainer = Trainer(config, appearance_embeddings=getattr(dataset, "appearance_embeddings", None),
                       n_images=len(dataset), group=group, near=getattr(dataset, "near", None),
-                      far=getattr(dataset, "far", None))
+                      far=getattr(dataset, "far", None), occupancy=occupancy, occupancy_refresh=occupancy_refresh)
     iters = config.num_iterations if num_iterations is None else num_iterations
     losses, psnrs = [], []
     train_nerf.losses, train_nerf.psnrs = losses, psnrs

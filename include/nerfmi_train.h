@@ -63,7 +63,56 @@ int nerf_train_backward(const float* packed, const float* packedT, const float* 
                         float* const* param_grads, float* dapp, float* loss, void* workspace,
                         size_t ws_bytes, nerf_stream_t stream);
 
+/* ------------------------------------------------ training with an occupancy grid
+ * The whole step on the samples an occupancy grid marks live (nerfmi.h "occupancy grid": the same
+ * float rule decides liveness).  A dead sample has sigma = 0 and rgb = 0 before compositing, as a
+ * constant of the step: its weight is exactly 0, it multiplies the transmittance by 1 + 1e-10 like
+ * any sigma = 0 sample, the MLP is not run on it and no gradient flows through it.  z_out is that of
+ * nerf_train_forward for the same seed.  f16x3 only (NERF_ERR_UNSUPPORTED under NERF_ARITH_F32);
+ * app_rows is 0 or 1 (per-ray appearance rows: NERF_ERR_UNSUPPORTED); B*N <= 2^30.
+ *
+ * Three calls, because the library never synchronises and the live count must reach the host once:
+ *   nerf_train_occ_sample    normalises the directions, draws the stratified z (the draws of
+ *                            nerf_train_forward for the same seed) and classifies: the ascending live
+ *                            list in the workspace, its length in *live_count (device int32).  Needs
+ *                            no weights.
+ *   (the caller copies *live_count to the host and waits for it)
+ *   nerf_train_occ_forward   ray features, the gathered forward, the dense composite.
+ *                            PRECONDITION: M_live == *live_count of the sample call on this workspace.
+ *   nerf_train_occ_backward  loss and gradients as nerf_train_backward; M_live as in the forward
+ *                            (NERF_ERR_BAD_ARG if no such forward wrote the workspace).  With
+ *                            M_live = 0 every gradient (and dapp) is written as zeros and the loss is
+ *                            that of the all-zero rgb_map.
+ * The workspace (nerf_train_occ_workspace_bytes, sized for every sample live; 0 for bad shapes) is
+ * nerf_train_forward's plus the live list, the classify block counts and the compact sigma, rgb,
+ * dsigma, drgb rows; save, mask and gradient rows hold M_live compact rows in the per-row layout
+ * (enc_d in every save row, as N < 32). */
+size_t nerf_train_occ_workspace_bytes(int64_t B, int N);
+int nerf_train_occ_sample(const float* rays_o, const float* rays_d, int64_t B, double near, double far, int N,
+                          const float* t_vals, int perturb, const float* t_rand, uint64_t seed,
+                          const uint32_t* bits, int G, const float* lo, const float* inv, int32_t* live_count,
+                          void* workspace, size_t ws_bytes, nerf_stream_t stream);
+int nerf_train_occ_forward(const float* packed, const float* rays_o, int64_t B, int N, int64_t M_live,
+                           const float* app, int64_t app_rows, float* rgb_map, float* depth_map,
+                           float* weights_out, float* z_out, void* workspace, size_t ws_bytes,
+                           nerf_stream_t stream);
+int nerf_train_occ_backward(const float* packed, const float* packedT, const float* rgb_map, const float* target,
+                            int64_t B, int N, int64_t M_live, const float* app, int64_t app_rows,
+                            float* const* param_grads, float* dapp, float* loss, void* workspace, size_t ws_bytes,
+                            nerf_stream_t stream);
+
 /* -------------------------------------------------------------------- stages */
+/* nerf_mlp_forward_train (f16x3 only) on the M_live samples the ascending list `live` names (sample
+ * r*N + s of the (R, N) launch): COMPACT row i is sample live[i].  save (NERF_TILE_ROWS(M_live) rows),
+ * masks (M_live rows), rgb_live (M_live,3) and sigma_live (M_live) are what nerf_mlp_forward_train at
+ * N = 1 writes for the gathered inputs, bit for bit (enc_d in every row, the block exponents of each
+ * 32 compact rows, zero padding rows); rgb and sigma (R*N rows) get the listed rows, the others are
+ * left untouched.  M_live = 0 launches nothing. */
+int nerf_mlp_forward_train_live(const float* packed, const float* origins, const float* dirs,
+                                const float* z_vals, int64_t R, int N, const float* ray_feat,
+                                const float* enc_d, const int32_t* live, int64_t M_live, float* rgb,
+                                float* sigma, float* rgb_live, float* sigma_live, float* save,
+                                uint32_t* masks, nerf_stream_t stream);
 /* W^T of trunk layers 1..7 and of dir_linear's h-part in MFMA fragment layout. */
 size_t nerf_packed_transposed_floats(void);
 int nerf_pack_weights_transposed(const float* const* params, float* packedT, nerf_stream_t stream);

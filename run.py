@@ -13,7 +13,10 @@ Added flags: --random_init SEED renders a seeded random-init model when no check
 ignores n_importance, render.py:83-86) with --n_importance samples; --chunk renders the frame
 in ray chunks (0 = whole frame per call); --occupancy RES builds an occupancy grid of RES^3 cells over
 [-X, X]^3 (--occupancy_bound X, default 1.5) from the loaded model once and skips the samples outside
-its set cells in every frame (nerfmi.OccupancyGrid; not a reference feature).  Under torchrun every frame is ray-sharded across
+its set cells in every frame (nerfmi.OccupancyGrid; not a reference feature); in --mode train the
+same two flags train on the live samples of a RES^3 grid over that box, which the trainer keeps
+current from its own model (all ones for the first 256 steps, then rebuilt every 256 steps), and the
+checkpoints carry the grid.  Under torchrun every frame is ray-sharded across
 the ranks (frames.py) and rank 0 writes the images.
 --mode train runs the reference's training loop (run.py:326-347 -> src/train.py) on the nerfmi
 kernels (nerfmi.train.train_nerf; the nerf_synthetic scene when present, else the
@@ -244,8 +247,14 @@ def main(argv=None):
         dataset = make_dataset(config)
         model_dimension_check(config)                                  # run.py:327-345
         torch.manual_seed(args.random_init or 0)
+        occ_kw = {}
+        if args.occupancy:   # train on the live samples of a grid the trainer keeps current (train.py, Trainer)
+            x = float(args.occupancy_bound)
+            occ_kw = dict(occupancy=nerfmi.OccupancyGrid((-x,) * 3, (x,) * 3, args.occupancy), occupancy_refresh={})
+            if rank == 0:
+                print(f"Training with an occupancy grid {args.occupancy}^3 over [-{x:g}, {x:g}]^3")
         model = train_nerf(config, dataset, save_dir=args.save_dir, num_iterations=args.iterations,   # run.py:347
-                           group=group)
+                           group=group, **occ_kw)
         if group is not None:
             dist.destroy_process_group()
         return 0
