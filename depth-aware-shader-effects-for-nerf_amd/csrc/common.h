@@ -58,7 +58,7 @@ __device__ __forceinline__ _Float16 split_lo(float x, _Float16 hi) {
 // bit-identical to split_lo; the compiler, given the same expression, converts both halves back to
 // f32 and packs the residuals with a third convert (or SLP-packs them into v_pk_fma_f32).  Used by
 // the training forward (mlp16.hip, issue-bound: 1.28 -> 1.19 ms, same-box A/B) and the data
-// gradient's row split (train.hip); the render kernel measured -0.3 % with it and keeps its own.
+// gradient's row split (mlp_backward.hip); the render kernel measured -0.3 % with it and keeps its own.
 __device__ __forceinline__ uint32_t split_lo_pair(uint32_t hi2, float x0, float x1) {
   uint32_t lo;
   asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"

@@ -14,6 +14,7 @@
 // lane l holding W[nt*32 + (l&31)][col(ks, l>>5)] for ks = 4*kq .. 4*kq+3, so one
 // wave reads a block with one coalesced 16-byte-per-lane load.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 #include <stddef.h>
 
@@ -167,6 +168,43 @@ NERF_HD inline int s16_exponent(float m) {
   return e;   // m = v * 2^e, v in [0.5, 1): m < 2^e
 }
 
+// ---- transposed weights (nerf_pack_weights_transposed; packers and readers in mlp_backward.hip) ----
+// Fragment layout (above) of W_l^T for trunk layers 1..7 (act part of layer 4) and of the
+// h-part of dir_linear: matrix mt = 0..6 is W_{mt+1}^T (256 x 256), mt = 7 is W_dh^T (256 x 128).
+// Rows are the forward layer's INPUT neurons (natural order), columns its OUTPUT neurons in the
+// accumulator k order, so the backward chain feeds d pre-activations to the MFMA as they sit
+// in registers, exactly like the forward.
+NERF_HD constexpr int tmat_ksteps(int mt) { return mt == 7 ? kDirHidden / 2 : kActSteps; }
+NERF_HD constexpr size_t tmat_offset(int mt) { return (size_t)mt * 8 * kActSteps * 64; }
+constexpr size_t kPackedT32Floats = tmat_offset(7) + (size_t)8 * (kDirHidden / 2) * 64;   // 491520
+// Split-f16 part (mlp_backward16_kernel), after the f32 part: W^T s_w of the same 8 matrices as f16
+// hi/lo A fragments of v_mfma_f32_32x32x16_f16.  Matrix mt holds 2 tile groups x KS16 k-steps x
+// 4 tiles x {hi, lo} pieces, each 64 lanes x 8 halves (4 words); the kernel streams them in that
+// order.  Lane l of the piece for (tile tt, k-step ks) holds W^T[32 tt + (l & 31)][n_j], the
+// k index n_j = 32 (ks >> 1) + 16 (ks & 1) + 8 (j >> 2) + 4 (l >> 5) + (j & 3) being the
+// accumulator order in which the previous backward layer leaves its outputs (act_feature).
+// s_w = 2^(14 - e) with max |W| < 2^e per matrix (s16_exponent), and its inverse, follow.
+// The matrices lie in the order the data-gradient chain consumes them (dir_linear's h-part, then
+// trunk layers 7 .. 1), so the f16 part is one contiguous stream of 16 KiB chunks (stream16.h):
+// chunk c of the stream is at kPackedT32Floats + c * kChunkFloats.
+NERF_HD constexpr int t16_ksteps(int mt) { return mt == 7 ? kDirHidden / 16 : kHidden / 16; }
+NERF_HD constexpr size_t t16_offset(int mt) {
+  return kPackedT32Floats + (mt == 7 ? 0 : (size_t)8 * kChunkFloats + (size_t)(6 - mt) * 16 * kChunkFloats);
+}
+constexpr int kBwChunks = 8 + 7 * 16;                                         // chunks of the stream
+constexpr size_t kOffT16Consts = kPackedT32Floats + (size_t)kBwChunks * kChunkFloats;
+// constants: s_w[8], 1/s_w[8], then the data-gradient bound constants C[8] (matrix mt's largest
+// row L1 norm of W^T, x 1.0001: |W^T g| <= C max|g| rigorously) and max |density_head.weight|
+constexpr int kT16S = 0, kT16InvS = 8, kT16C = 16, kT16WsigMax = 24, kT16Consts = 32;
+constexpr size_t kPackedTFloats = kOffT16Consts + kT16Consts;                 // 983072
+NERF_HD inline void store_t16_consts(float* consts, int mt, float mx) {
+  const int e = s16_exponent(mx);
+  consts[kT16S + mt] = ldexpf(1.0f, 14 - e);
+  consts[kT16InvS + mt] = ldexpf(1.0f, e - 14);
+}
+static_assert(t16_offset(0) + 16 * kChunkFloats == kOffT16Consts && t16_offset(6) == t16_offset(7) + 8 * kChunkFloats,
+              "the transposed stream is contiguous in consumption order");
+
 }  // namespace nerf
 
 namespace nerf {
@@ -181,7 +219,7 @@ constexpr int kSaveEncX = 4 * kHidden;                       // 1024
 NERF_HD constexpr int save_h(int l) { return l < 4 ? l * kHidden : kSaveEncX + 64 + (l - 4) * kHidden; }
 constexpr int kSaveEncD = 1088 + 4 * kHidden;                // 2112
 // enc_d is constant along a ray: rays of N >= kEncDPerRayMinN samples carry it in their first
-// sample's row only (the weight gradients read it per ray there, train.hip param_grads); shorter rays
+// sample's row only (the weight gradients read it per ray there, train_api.hip param_grads); shorter rays
 // in every row (the dir GEMM reads [h7 | enc_d] per sample)
 constexpr int kEncDPerRayMinN = 32;
 constexpr int kSaveRDir = kSaveEncD + 32;                    // 2144

@@ -42,21 +42,6 @@
 
 namespace nerf {
 
-#ifdef NERF_MLP16_STAMPS   // diagnostic build: per-wave segment clocks (the render kernel's: mlp16s.hip STAMP16S)
-__device__ unsigned long long nerf16_stamps[65536][16];
-#define STAMP16(i)                                                                          \
-  do {                                                                                      \
-    __builtin_amdgcn_sched_barrier(0);                                                      \
-    unsigned long long t_;                                                                  \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");            \
-    __builtin_amdgcn_sched_barrier(0);                                                      \
-    const int64_t w_ = (int64_t)blockIdx.x * kW16Waves + wave;                              \
-    if (w_ < 65536 && lane == 0) nerf16_stamps[w_][i] = t_;                                 \
-  } while (0)
-#else
-#define STAMP16(i) do {} while (0)
-#endif
-
 // ---- LDS: one __shared__ array (a second object can make hipcc drain the DMA before every
 // ds_read).  [ring: 4 x 16 KiB][PE: 4 waves x 32 x 64][biases 8 x 256 | density_head w 256, b 4]
 // [layer constants].  Every small vector the layers read sits here: an ordinary global load used
@@ -99,7 +84,7 @@ struct SaveAt {      // training forward: where a layer's activations go (see co
 };
 // ReLU-mask bits of tile T (quarter q, element e -> bit 4q + e: neuron 32T + 8q + 4h + e) go to
 // bits 16 (T % 2) of word T / 2 of the lane's 4-word (16-byte) slot of the layer: exactly the
-// 128-bit mask the backward folds from the activations (train.hip dgrad16), so it loads one slot.
+// 128-bit mask the backward folds from the activations (mlp_backward.hip dgrad16), so it loads one slot.
 // One ds_or per quarter: no register lives across quarters.
 __device__ __forceinline__ void mask_or(const SaveAt& sv, int T, uint32_t bits) {
   __hip_atomic_fetch_or(sv.mrow + sv.mlay + T / 2, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);

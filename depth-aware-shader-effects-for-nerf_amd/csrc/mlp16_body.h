@@ -27,7 +27,6 @@ mlp16_kernel(const float* __restrict__ packed, const float* __restrict__ orig, c
 #endif
   __shared__ __attribute__((aligned(16))) float lds[SAVE ? kLdsFloatsSave : kLdsFloats];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, h = lane >> 5;
-  STAMP16(0);
   const int64_t s0 = ((int64_t)blockIdx.x * kW16Waves + wave) * 32;
   // every wave runs to the end (the weight stream has barriers); tail lanes repeat sample M-1
   const bool valid = s0 + (lane & 31) < M;
@@ -139,7 +138,6 @@ mlp16_kernel(const float* __restrict__ packed, const float* __restrict__ orig, c
   float bexp = (lane & 31) == 8 ? rec_encx : 0.0f;
   float inv_cur = cst[kS16InvW + 0] / s_cur;                // exact: powers of two
   float s_nxt = pow2_scale(cst[kS16R + 0] * m_pe + cst[kS16B + 0]);
-  STAMP16(1);
 
   // ---- layer 0: PE(63) -> 256, 2 chunk-steps per group ----
   auto pe_operand_of = [&](auto i, auto kk) -> const Operand& { return pe_op[kstep_of(i, kk)]; };
@@ -159,7 +157,6 @@ mlp16_kernel(const float* __restrict__ packed, const float* __restrict__ orig, c
                                                acc, inv_cur, bias, ws, h, s_nxt, in, m, part, qv[j], sv_cur);
                                          });
                                        });
-  STAMP16(2);
 
   // ---- layers 1..7 ----
   // On entry to layer L: operands 0..7 hold y_{L-1} tiles 0-3 split at s_cur, y_{L-1} tiles 4-7
@@ -258,7 +255,6 @@ mlp16_kernel(const float* __restrict__ packed, const float* __restrict__ orig, c
     inv_prev = inv_cur;
     bias_prev = bias_l;
     s_cur = s_nxt;
-    STAMP16(2 + L);
   };
 #pragma unroll 1
   for (int L = 1; L < kSkipLayer; ++L) layer(L, NoSigma{}, NoSigma{});
@@ -299,7 +295,6 @@ mlp16_kernel(const float* __restrict__ packed, const float* __restrict__ orig, c
   }
   run_group<0, 8, 0, 0, kSidePrev, SAVE>(stream, s16_chunk0(8), lds, lds_dma, voff, a0, a1, acc, lane, act_operand,
                         [&](auto i, auto kk, auto ph) __attribute__((always_inline)) { side_prev(i, kk, ph, Sigma{}); });
-  STAMP16(10);
   if constexpr (SAVE) {     // h_7 (m: y_7 tiles 0-3 from layer 7's group B, tiles 4-7 from the colour layer's)
     const float rec = block_exp_record(wave_max_nn(sample_max(m)));
     bexp = (lane & 31) == 7 ? rec : bexp;
@@ -401,5 +396,4 @@ mlp16_kernel(const float* __restrict__ packed, const float* __restrict__ orig, c
 #pragma unroll
     for (int c = 0; c < 3; ++c) rgb[3 * o_s + c] = out[c];
   }
-  STAMP16(11);
 }

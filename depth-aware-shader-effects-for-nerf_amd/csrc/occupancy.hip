@@ -153,7 +153,7 @@ int launch_occ_classify(const float* o, const float* d, const float* z, int64_t 
   return check_launch("occ_write_kernel");
 }
 
-// Training with a grid (train.hip, nerf_train_occ_backward): the composite backward runs dense on
+// Training with a grid (train_api.hip, nerf_train_occ_backward): the composite backward runs dense on
 // (B, N); the rows of its dsigma / drgb that the live list names are gathered into the compact rows
 // the MLP backward reads.  What it formed at dead rows is dropped (sigma = 0 there is a constant).
 __global__ void __launch_bounds__(256) occ_gather_grads_kernel(const float* __restrict__ dsigma,

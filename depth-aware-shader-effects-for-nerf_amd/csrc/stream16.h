@@ -1,5 +1,5 @@
 // The split-f16 MFMA weight stream shared by the fused MLP forward (mlp16.hip) and the data-gradient
-// chain of the training backward (train.hip): the B-operand split, the 4-slot LDS ring that the 4
+// chain of the training backward (mlp_backward.hip): the B-operand split, the 4-slot LDS ring that the 4
 // waves of a workgroup fill by LDS-DMA three 16 KiB chunks ahead, and the chunk-step / group
 // drivers that interleave each k-step's MFMAs with the next k-step's fragment reads and with VALU
 // side work (the previous layer's epilogue).  mlp16.hip's header comment describes the schedule.
@@ -113,7 +113,7 @@ __device__ __forceinline__ void mfma_kstep(const h16x8 (&a)[4][2], const Operand
 enum SideKind { kSideNone, kSidePrev, kSideCur, kSideL0, kSideSkipPrev, kSideHalf };
 template <int KIND>
 __device__ __forceinline__ constexpr int side_quarters(int hs) {
-  if constexpr (KIND == kSideHalf) return 2;        // 16 quarters over an 8-k-step group (train.hip)
+  if constexpr (KIND == kSideHalf) return 2;        // 16 quarters over an 8-k-step group (mlp_backward.hip)
   if constexpr (KIND == kSidePrev) return hs == 0 ? 2 : (hs <= 14 ? 1 : 0);
   if constexpr (KIND == kSideSkipPrev) return hs == 0 ? 2 : (hs <= 18 ? 1 : 0);   // + PE operands at 15..18
   if constexpr (KIND == kSideCur) return hs == 15 ? 2 : (hs >= 1 && hs <= 14 ? 1 : 0);

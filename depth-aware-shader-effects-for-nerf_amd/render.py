@@ -33,7 +33,7 @@ and ``background_color``.  Keyword-only extras:
 With gradients enabled and a trainable model (or an appearance embedding that requires grad),
 the reference-compat call (coarse; hierarchical, staged and timing unset) runs the training
 kernels instead (autograd.py): rgb_map and depth_map carry a grad_fn whose backward is the
-composite backward + MLP data-gradient chain + weight-gradient reductions of csrc/train.hip, as
+composite backward + MLP data-gradient chain + weight-gradient reductions of csrc/composite_bwd.hip, mlp_backward.hip and train.hip, as
 the reference's training loop needs (src/train.py:77-92).  The H1 hierarchical pass has no
 reference training semantics (render.py:83-86 is a stub): with gradients enabled and a trainable
 model it raises (RuntimeError naming hierarchical=True) instead of silently returning no graph.

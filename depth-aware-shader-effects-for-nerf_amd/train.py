@@ -5,7 +5,7 @@ One iteration (train.py:77-92) is: volume_render(perturb=True) over a batch of r
 calls (include/nerfmi_train.h) and one RCCL all-reduce:
 
   nerf_train_forward    normalise, stratified samples, fused PE→MLP forward on MFMA saving every
-                        activation, composite (csrc/train.hip, csrc/mlp.hip)
+                        activation, composite (csrc/train_api.hip, csrc/mlp.hip, csrc/mlp16.hip)
   nerf_train_backward   loss, composite backward (reverse scan), MLP data-gradient chain on MFMA
                         with transposed weight fragments, every weight gradient as an MFMA
                         reduction over the batch, appearance-row gradient

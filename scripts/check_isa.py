@@ -1,5 +1,5 @@
 """Build-time guard of the M0 register in the LDS-DMA weight streams (csrc/mlp16.hip, csrc/mlp16s.hip,
-csrc/train.hip).
+csrc/mlp_backward.hip).
 
 The streams issue `s_mov_b32 m0, <lds address>` + `global_load_lds_dwordx4` from inline asm and declare
 M0 clobbered; the compiler is never told the value must survive, so the kernels are only correct

@@ -1,6 +1,6 @@
 """Where two identically seeded trainers (tests/test_gpu_train.py::test_training_is_deterministic's
 setup) first diverge: per step, per-column bit checksums of the training workspace's save rows, mask
-rows and gradient rows (nerf_train_forward / nerf_train_backward's carve, csrc/train.hip train_carve),
+rows and gradient rows (nerf_train_forward / nerf_train_backward's carve, csrc/train_api.hip train_carve),
 the parameter gradients and the parameters.  NERFMI_LIB selects the library.  Diagnostic, not a test."""
 import os
 import sys

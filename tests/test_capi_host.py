@@ -429,7 +429,7 @@ def test_transposed_split_f16_fragments(ref_state):
 
 
 def emulate_backward(packed, packedT, x, d, app, g_rgb, g_sigma):
-    """The backward kernel's dataflow (csrc/train.hip mlp_backward_kernel) in float64: the
+    """The backward kernel's dataflow (csrc/mlp_backward.hip mlp_backward_kernel) in float64: the
     transposed fragments applied to d pre-activations in accumulator order, returning the
     gradient with respect to the PE input and to every trunk pre-activation."""
     off_bias = frag_offset(10)

@@ -197,7 +197,7 @@ def test_gradients_vs_float64(which, ref_state, app_vec, trained_state, arith):
 
     Bounds, per tensor (rel-L2 against float64), the same for both arithmetics: within 2x the fp32 CPU
     autograd's own error, +1e-6 for tensors both get to ~eps.  Under f16x3 that holds because the data
-    gradient splits odd samples at a negative scale (train.hip, mlp_backward16_bound_kernel): the MFMA
+    gradient splits odd samples at a negative scale (mlp_backward.hip, mlp_backward16_bound_kernel): the MFMA
     unit's f32 accumulation of f16 products is not correctly rounded and leans negative (-0.12 ulp on
     average, profiles/r04/mfma_f16_accumulation_rounding.log), and without the sign flip that one-signed
     error added up over the samples of a bias gradient, where the true values cancel: 6.2e-6 on

@@ -1,6 +1,6 @@
 """Training with an occupancy grid on the GPU (include/nerfmi_train.h "training with an occupancy
 grid"): the gathered training forward (csrc/mlp16.hip, mlp16_live_kernel), the
-whole-step entry points (csrc/train.hip) and the Trainer plumbing.
+whole-step entry points (csrc/train_api.hip) and the Trainer plumbing.
 
 The main criterion is bit-identity with compositions of the existing stage entry points: the gathered
 forward equals nerf_mlp_forward_train at N = 1 on the gathered inputs, and the whole step equals
