@@ -2,7 +2,7 @@
 
 The reference trains by rendering with gradients enabled and calling ``loss.backward()``
 (src/train.py:77-92); its run.py train mode also calls ``model(x, d, app)`` with gradients
-enabled (run.py:338-345).  Here both run the training kernels (csrc/composite_bwd.hip, mlp_backward.hip, train.hip; entry points in csrc/train_api.hip) through the C ABI
+enabled (run.py:338-345).  Here both run the training kernels (csrc/composite_bwd.hip, mlp_backward.hip, wgrad.hip; entry points in csrc/train_api.hip) through the C ABI
 (include/nerfmi_train.h), wrapped in two ``torch.autograd.Function``s:
 
   _RenderFn   volume_render (render.py:5-97, coarse; n_importance ignored as in :83-86)

@@ -9,7 +9,7 @@
 
 #include <vector>
 
-#include "common.h"
+#include "host_api.h"
 
 namespace nerf {
 
@@ -252,16 +252,40 @@ static void pack_host(const float* const* P, float* packed) {
   for (size_t w = 0; w < kFragFloats; ++w) words[kOff16 + w] = pack16_word(P, consts, w);
 }
 
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace nerf
 
 using namespace nerf;
 
-#define REQUIRE(cond, ...)                                   \
-  do {                                                       \
-    if (!(cond)) return set_error(NERF_ERR_BAD_ARG, __VA_ARGS__); \
-  } while (0)
+// ------------------------------------------------------------------ MLP launch profiling
+// bench.py's roofline leg: while on, every fused-MLP launch (nerf_render_rays' two, or
+// nerf_mlp_forward's one) is bracketed by HIP events recorded on the launch's own stream, so the
+// shipped single-call path is timed per launch with no change to what it runs.  One process-wide
+// recorder (a diagnostic for one host thread).
+namespace {
+struct MlpProfile {
+  std::vector<hipEvent_t> ev;
+  std::vector<int64_t> samples;
+  int n = 0;
+  bool on = false;
+};
+MlpProfile g_prof;
+}  // namespace
+
+// One MLP launch (the callable) behind the profiling hook; `samples` is the launch's R N (the
+// gathered kernel's live count stays on the device).
+template <typename Launch>
+static int profiled(hipStream_t s, int64_t samples, Launch&& launch) {
+  const bool rec = g_prof.on && g_prof.n < (int)g_prof.samples.size();
+  if (rec && hipEventRecord(g_prof.ev[2 * g_prof.n], s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "nerf profile: hipEventRecord failed");
+  if (int rc = launch()) return rc;
+  if (rec) {
+    if (hipEventRecord(g_prof.ev[2 * g_prof.n + 1], s) != hipSuccess)
+      return set_error(NERF_ERR_HIP, "nerf profile: hipEventRecord failed");
+    g_prof.samples[g_prof.n++] = samples;
+  }
+  return NERF_OK;
+}
 
 extern "C" {
 
@@ -369,35 +393,6 @@ int nerf_ray_features(const float* packed, const float* dirs, int64_t R, const f
   return launch_ray_features(packed, dirs, R, app, app_rows, feat, (hipStream_t)stream);
 }
 
-// ------------------------------------------------------------------ MLP launch profiling
-// bench.py's roofline leg: while on, every fused-MLP launch (nerf_render_rays' two, or
-// nerf_mlp_forward's one) is bracketed by HIP events recorded on the launch's own stream, so the
-// shipped single-call path is timed per launch with no change to what it runs.  One process-wide
-// recorder (a diagnostic for one host thread).
-namespace {
-struct MlpProfile {
-  std::vector<hipEvent_t> ev;
-  std::vector<int64_t> samples;
-  int n = 0;
-  bool on = false;
-};
-MlpProfile g_prof;
-}  // namespace
-
-static int profiled_mlp(const float* packed, const float* origins, const float* dirs, const float* z, int64_t R,
-                        int N, const float* feat, float* rgb, float* sigma, const int* slot, int T, hipStream_t s) {
-  const bool rec = g_prof.on && g_prof.n < (int)g_prof.samples.size();
-  if (rec && hipEventRecord(g_prof.ev[2 * g_prof.n], s) != hipSuccess)
-    return set_error(NERF_ERR_HIP, "nerf profile: hipEventRecord failed");
-  if (int rc = launch_mlp(packed, origins, dirs, z, R, N, feat, rgb, sigma, slot, T, s)) return rc;
-  if (rec) {
-    if (hipEventRecord(g_prof.ev[2 * g_prof.n + 1], s) != hipSuccess)
-      return set_error(NERF_ERR_HIP, "nerf profile: hipEventRecord failed");
-    g_prof.samples[g_prof.n++] = R * (int64_t)N;
-  }
-  return NERF_OK;
-}
-
 int nerf_profile_mlp_begin(int capacity) {
   REQUIRE(capacity >= 1 && capacity <= 1 << 20, "nerf_profile_mlp_begin: capacity=%d", capacity);
   for (hipEvent_t e : g_prof.ev) (void)hipEventDestroy(e);
@@ -460,9 +455,11 @@ int nerf_mlp_forward(const float* packed, const float* origins, const float* dir
   for (int64_t r0 = 0; r0 < R; r0 += rc_rays) {            // (one chunk unless R N > 2^30)
     const int64_t n = R - r0 < rc_rays ? R - r0 : rc_rays;
     const int64_t orow = out_slot ? (int64_t)out_T : (int64_t)N;   // output rows per ray
-    if (int rc = profiled_mlp(packed, origins + 3 * r0, dirs ? dirs + 3 * r0 : nullptr, z_vals ? z_vals + r0 * N : nullptr,
-                              n, N, ray_feat + r0 * kRayFeat, rgb + 3 * r0 * orow, sigma + r0 * orow,
-                              out_slot ? out_slot + r0 * N : nullptr, out_T, (hipStream_t)stream))
+    if (int rc = profiled((hipStream_t)stream, n * (int64_t)N, [&] {
+          return launch_mlp(packed, origins + 3 * r0, dirs ? dirs + 3 * r0 : nullptr, z_vals ? z_vals + r0 * N : nullptr,
+                            n, N, ray_feat + r0 * kRayFeat, rgb + 3 * r0 * orow, sigma + r0 * orow,
+                            out_slot ? out_slot + r0 * N : nullptr, out_T, (hipStream_t)stream);
+        }))
       return rc;
   }
   return NERF_OK;
@@ -476,140 +473,12 @@ int nerf_composite(const float* rgb, const float* sigma, const float* z_vals, in
   return launch_composite(rgb, sigma, z_vals, B, N, rgb_map, depth_map, weights, (hipStream_t)stream);
 }
 
-// Workspace carve of nerf_render_rays, in this order (each region 256-B aligned), T = N + Nf:
-//   dirs (B,3) | z (B,N) | feat (B,256) | rgb_c (B,N,3) | sigma_c (B,N) | w_c (B,N) | z_all (B,T)
-//   | z_fine (B,Nf) | merged_src (B,T) uint16 | rgb_f (B,Nf,3) | sigma_f (B,Nf) | maps (B,4)
-enum { W_DIRS, W_Z, W_FEAT, W_RGBC, W_SIGC, W_WC, W_ZALL, W_ZF, W_SRC, W_RGBF, W_SIGF, W_MAPS, W_COUNT };
-
-static size_t carve(int64_t B, int N, int Nf, size_t* off) {
-  const size_t T = (size_t)N + Nf, b = (size_t)B;
-  const size_t sizes[W_COUNT] = {b * 3, b * N, b * kRayFeat, b * N * 3, b * N, b * N, b * T,
-                                 b * Nf, (b * T + 1) / 2, b * Nf * 3, b * Nf, b * 4};
-  size_t at = 0;
-  for (int i = 0; i < W_COUNT; ++i) {
-    off[i] = at;
-    at += align_up(sizes[i] * 4);
-  }
-  return at;
-}
-
-int64_t nerf_render_chunk_rays(int N, int Nf);
-
-// (one chunk's worth: the chunks of a call past the launch-size limit reuse it in stream order)
-size_t nerf_render_workspace_bytes(int64_t B, int N, int Nf) {
-  if (B < 0 || N < 1 || Nf < 0) return 0;
-  const int64_t chunk = nerf_render_chunk_rays(N, Nf);
-  size_t off[W_COUNT];
-  return carve(B < chunk ? B : chunk, N, Nf, off);
-}
-
-static int render_rays_chunk(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
-                             double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
-                             const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0, const float* app,
-                             int64_t app_rows, float* rgb_map, float* depth_map, float* weights_out, float* z_out,
-                             float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
-                             nerf_stream_t stream);
-
-int nerf_render_rays(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
-                     double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
-                     const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0, const float* app,
-                     int64_t app_rows, float* rgb_map, float* depth_map, float* weights_out, float* z_out,
-                     float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
-                     nerf_stream_t stream) {
-  REQUIRE(B >= 0 && ray0 >= 0, "nerf_render_rays: B=%lld ray0=%lld", (long long)B, (long long)ray0);
-  if (N < 1 || N > 4096 || Nf < 0 || N + Nf > 4096 || (Nf > 0 && (N > 256 || Nf > 1024)))
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_render_rays: N=%d Nf=%d outside the supported range", N, Nf);
-  // calls past the launch-size limit run in ray chunks: every per-ray input and output advances by
-  // the chunk's first ray, the in-kernel draws stay keyed by the global ray index (ray0 + c0), and
-  // each chunk carves the caller's workspace for its own (smaller) B
-  REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "nerf_render_rays: app_rows=%lld with B=%lld",
-          (long long)app_rows, (long long)B);
-  const int64_t chunk = nerf_render_chunk_rays(N, Nf);
-  if (chunk < 1)   // (N + Nf <= 4096 <= the launch limit: unreachable, but never loop on a zero step)
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_render_rays: N=%d Nf=%d exceed the launch limit", N, Nf);
-  const int64_t T = Nf > 0 ? (int64_t)N + Nf : (int64_t)N;   // weights_out / z_out columns
-  for (int64_t c0 = 0; c0 < B || (B == 0 && c0 == 0); c0 += chunk) {
-    const int64_t n = B - c0 < chunk ? B - c0 : chunk;
-    const bool per_ray_app = app_rows > 1;
-    if (int rc = render_rays_chunk(packed, rays_o + 3 * c0, rays_d + 3 * c0, n, near, far, N, Nf, t_vals, u_lin, perturb,
-                                   t_rand ? t_rand + c0 * N : nullptr, u_rand ? u_rand + c0 * Nf : nullptr, seed,
-                                   ray0 + c0, per_ray_app ? app + c0 * kAppDim : app, per_ray_app ? n : app_rows,
-                                   rgb_map + 3 * c0, depth_map + c0, weights_out ? weights_out + c0 * T : nullptr,
-                                   z_out ? z_out + c0 * T : nullptr, coarse_rgb ? coarse_rgb + 3 * c0 : nullptr,
-                                   coarse_depth ? coarse_depth + c0 : nullptr, workspace, ws_bytes, stream))
-      return rc;
-    if (B == 0) break;
-  }
-  return NERF_OK;
-}
-
-static int render_rays_chunk(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
-                             double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
-                             const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0, const float* app,
-                             int64_t app_rows, float* rgb_map, float* depth_map, float* weights_out, float* z_out,
-                             float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
-                             nerf_stream_t stream) {
-  if (N < 1 || N > 4096 || Nf < 0 || N + Nf > 4096 || (Nf > 0 && (N > 256 || Nf > 1024)))
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_render_rays: N=%d Nf=%d outside the supported range", N, Nf);
-  if (B == 0) return NERF_OK;
-  REQUIRE(packed && rays_o && rays_d && t_vals && rgb_map && depth_map && workspace, "nerf_render_rays: null pointer");
-  REQUIRE(Nf == 0 || u_lin, "nerf_render_rays: u_lin required when Nf > 0");
-  REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "nerf_render_rays: app_rows=%lld with B=%lld",
-          (long long)app_rows, (long long)B);
-  REQUIRE(app_rows == 0 || app, "nerf_render_rays: null appearance");
-  size_t off[W_COUNT];
-  const size_t need = carve(B, N, Nf, off);
-  if (ws_bytes < need)
-    return set_error(NERF_ERR_WORKSPACE, "nerf_render_rays: workspace %zu < %zu bytes", ws_bytes, need);
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  auto region = [&](int i) { return (float*)(ws + off[i]); };
-  float* dn = region(W_DIRS);
-  float* z = (Nf == 0 && z_out) ? z_out : region(W_Z);
-  float* feat = region(W_FEAT);
-  float* rgb_c = region(W_RGBC);
-  float* sigma_c = region(W_SIGC);
-  float* wc = (Nf == 0) ? weights_out : region(W_WC);
-  float* z_all = z_out ? z_out : region(W_ZALL);
-  float* maps = region(W_MAPS);
-  // in-kernel draws keyed by the global ray index ray0 + r (nerf_rng_uniforms)
-  const uint64_t seed_c = rng_key_at(seed, (uint64_t)ray0 * (uint64_t)N);
-  const uint64_t seed_f = rng_key_at(seed ^ 0x5DEECE66Dull, (uint64_t)ray0 * (uint64_t)Nf);
-  int rc;
-  // render.py:19's normalisation in the ray-feature kernel (it writes dn)
-  if ((rc = launch_ray_features(packed, rays_d, B, app, app_rows, feat, s, nullptr, dn))) return rc;
-  if ((rc = launch_stratified(rays_o, dn, B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand, seed_c,
-                              z, nullptr, s)))
-    return rc;                                                                                 // render.py:22
-  if ((rc = profiled_mlp(packed, rays_o, dn, z, B, N, feat, rgb_c, sigma_c, nullptr, 0, s))) return rc;  // :49
-  if (Nf == 0)
-    return launch_composite(rgb_c, sigma_c, z, B, N, rgb_map, depth_map, wc, s);               // render.py:56-80
-  float* crgb = coarse_rgb ? coarse_rgb : maps;
-  float* cdepth = coarse_depth ? coarse_depth : maps + 3 * B;
-  if ((rc = launch_composite(rgb_c, sigma_c, z, B, N, crgb, cdepth, wc, s))) return rc;
-  // H1 fine pass: resample + merge (each merged slot records which coarse or fine sample it holds),
-  // the MLP run on the Nf new samples only, in sample order, and the composite over all N+Nf merged
-  // samples gathering the coarse evaluations and the fine ones through the map.  (Round 3 scattered
-  // the coarse results into merged rows and the fine MLP wrote into its slots: 4.0 GB written by
-  // the resample and 24 B per fine sample by the MLP, for the same bits.)
-  float* z_fine = region(W_ZF);
-  uint16_t* msrc = (uint16_t*)region(W_SRC);
-  float* rgb_f = region(W_RGBF);
-  float* sigma_f = region(W_SIGF);
-  if ((rc = launch_importance(nullptr, nullptr, z, wc, B, N, Nf, u_lin, u_rand, seed_f, z_all, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, z_fine, nullptr, s, msrc)))
-    return rc;
-  if ((rc = profiled_mlp(packed, rays_o, dn, z_fine, B, Nf, feat, rgb_f, sigma_f, nullptr, 0, s))) return rc;
-  return launch_composite_merged(rgb_c, sigma_c, rgb_f, sigma_f, msrc, z_all, B, N, Nf, rgb_map, depth_map,
-                                 weights_out, s);
-}
-
 // --------------------------------------------------------------- occupancy-grid sample skipping
 // (include/nerfmi.h; kernels in occupancy.hip and mlp16s.hip's gathered entry)
-#define REQUIRE_GRID(fn, G)                                                                               \
-  do {                                                                                                    \
-    if ((G) < 1 || (G) > 1024) return set_error(NERF_ERR_UNSUPPORTED, fn ": G=%d outside 1..1024", (G)); \
-  } while (0)
+static int check_grid(const char* fn, int G) {
+  if (G < 1 || G > 1024) return set_error(NERF_ERR_UNSUPPORTED, "%s: G=%d outside 1..1024", fn, G);
+  return NERF_OK;
+}
 
 size_t nerf_occupancy_words(int G) {
   if (G < 1 || G > 1024) return 0;
@@ -619,7 +488,7 @@ size_t nerf_occupancy_words(int G) {
 int nerf_occupancy_pack(const float* sigma_lattice, int G, int s, float threshold, uint32_t* bits,
                         nerf_stream_t stream) {
   REQUIRE(sigma_lattice && bits, "nerf_occupancy_pack: null pointer");
-  REQUIRE_GRID("nerf_occupancy_pack", G);
+  if (int rc = check_grid("nerf_occupancy_pack", G)) return rc;
   REQUIRE(s >= 1 && (int64_t)s * G <= 4096, "nerf_occupancy_pack: s=%d probes per cell with G=%d (s G <= 4096)", s, G);
   return launch_occ_pack(sigma_lattice, G, s, threshold, bits, (hipStream_t)stream);
 }
@@ -627,13 +496,13 @@ int nerf_occupancy_pack(const float* sigma_lattice, int G, int s, float threshol
 int nerf_occupancy_dilate(const uint32_t* bits_in, int G, uint32_t* bits_out, nerf_stream_t stream) {
   REQUIRE(bits_in && bits_out, "nerf_occupancy_dilate: null pointer");
   REQUIRE(bits_in != bits_out, "nerf_occupancy_dilate: in place");
-  REQUIRE_GRID("nerf_occupancy_dilate", G);
+  if (int rc = check_grid("nerf_occupancy_dilate", G)) return rc;
   return launch_occ_dilate(bits_in, G, bits_out, (hipStream_t)stream);
 }
 
 size_t nerf_occupancy_classify_workspace_bytes(int64_t B, int n) {
   if (B < 0 || n < 1 || B * (int64_t)n > max_launch_samples()) return 0;
-  return align_up(occ_block_count_bytes(B * (int64_t)n));
+  return align256(occ_block_count_bytes(B * (int64_t)n));
 }
 
 int nerf_occupancy_classify(const float* rays_o, const float* dirs, const float* z, int64_t B, int n,
@@ -643,7 +512,7 @@ int nerf_occupancy_classify(const float* rays_o, const float* dirs, const float*
   REQUIRE(B >= 0 && n >= 1, "nerf_occupancy_classify: B=%lld n=%d", (long long)B, n);
   REQUIRE(bits && lo && inv && live_count, "nerf_occupancy_classify: null pointer");
   REQUIRE(B == 0 || (rays_o && dirs && z && live && workspace), "nerf_occupancy_classify: null pointer");
-  REQUIRE_GRID("nerf_occupancy_classify", G);
+  if (int rc = check_grid("nerf_occupancy_classify", G)) return rc;
   if (B * (int64_t)n > max_launch_samples())
     return set_error(NERF_ERR_UNSUPPORTED, "nerf_occupancy_classify: %lld samples exceed the launch limit %lld",
                      (long long)(B * (int64_t)n), (long long)max_launch_samples());
@@ -652,23 +521,6 @@ int nerf_occupancy_classify(const float* rays_o, const float* dirs, const float*
     return set_error(NERF_ERR_WORKSPACE, "nerf_occupancy_classify: workspace %zu < %zu bytes", ws_bytes, need);
   return launch_occ_classify(rays_o, dirs, z, B, n, bits, G, lo, inv, live, live_count, mask, nullptr, nullptr,
                              (uint32_t*)workspace, (hipStream_t)stream);
-}
-
-// The gathered MLP behind the profiling hook, as profiled_mlp (the recorded sample count is the
-// launch's R N: the live count stays on the device).
-static int profiled_mlp_live(const float* packed, const float* origins, const float* dirs, const float* z, int64_t R,
-                             int N, const float* feat, float* rgb, float* sigma, const int* live, const int* live_count,
-                             hipStream_t s) {
-  const bool rec = g_prof.on && g_prof.n < (int)g_prof.samples.size();
-  if (rec && hipEventRecord(g_prof.ev[2 * g_prof.n], s) != hipSuccess)
-    return set_error(NERF_ERR_HIP, "nerf profile: hipEventRecord failed");
-  if (int rc = launch_mlp16s_live(packed, origins, dirs, z, R, N, feat, rgb, sigma, live, live_count, s)) return rc;
-  if (rec) {
-    if (hipEventRecord(g_prof.ev[2 * g_prof.n + 1], s) != hipSuccess)
-      return set_error(NERF_ERR_HIP, "nerf profile: hipEventRecord failed");
-    g_prof.samples[g_prof.n++] = R * (int64_t)N;
-  }
-  return NERF_OK;
 }
 
 int nerf_mlp_forward_live(const float* packed, const float* origins, const float* dirs, const float* z_vals,
@@ -683,98 +535,208 @@ int nerf_mlp_forward_live(const float* packed, const float* origins, const float
   if (R * (int64_t)N > max_launch_samples())   // (the list indexes one launch: no chunking)
     return set_error(NERF_ERR_UNSUPPORTED, "nerf_mlp_forward_live: %lld samples exceed the launch limit %lld",
                      (long long)(R * (int64_t)N), (long long)max_launch_samples());
-  return profiled_mlp_live(packed, origins, dirs, z_vals, R, N, ray_feat, rgb, sigma, live, live_count,
-                           (hipStream_t)stream);
+  return profiled((hipStream_t)stream, R * (int64_t)N, [&] {
+    return launch_mlp16s_live(packed, origins, dirs, z_vals, R, N, ray_feat, rgb, sigma, live, live_count,
+                              (hipStream_t)stream);
+  });
 }
 
-// Workspace of nerf_render_rays_occ: the plain carve, then (each 256-B aligned) the live list
-// (B max(N, Nf) int32), the count and the classify block counts.
-enum { WO_LIVE, WO_COUNT, WO_BLOCKS, WO_COUNT_REGIONS };
-static size_t carve_occ(int64_t B, int N, int Nf, size_t* off, size_t* off_occ) {
-  size_t at = carve(B, N, Nf, off);
-  const int64_t per = B * (int64_t)(N > Nf ? N : Nf);
-  const size_t sizes[WO_COUNT_REGIONS] = {(size_t)per * 4, 4, occ_block_count_bytes(per)};
-  for (int i = 0; i < WO_COUNT_REGIONS; ++i) {
-    off_occ[i] = at;
-    at += align_up(sizes[i]);
+// ------------------------------------------------------------------------- the single-call render
+// Workspace of nerf_render_rays, in this order (each region 256-B aligned), T = N + Nf:
+//   dirs (B,3) | z (B,N) | feat (B,256) | rgb_c (B,N,3) | sigma_c (B,N) | w_c (B,N) | z_all (B,T)
+//   | z_fine (B,Nf) | merged_src (B,T) uint16 | rgb_f (B,Nf,3) | sigma_f (B,Nf) | maps (B,4)
+// and of nerf_render_rays_occ: the same, then the live list (B max(N, Nf) int32), the count and the
+// classify block counts.
+struct RenderWs {
+  float *dirs, *z, *feat, *rgb_c, *sigma_c, *w_c, *z_all, *z_fine;
+  uint16_t* merged_src;
+  float *rgb_f, *sigma_f, *maps;
+  int *live, *count;     // the occupancy tail (null without a grid)
+  uint32_t* blocks;
+};
+
+static size_t render_carve(int64_t B, int N, int Nf, bool occ, void* base, RenderWs& w) {
+  const size_t T = (size_t)N + Nf, b = (size_t)B;
+  Carver c{(char*)base};
+  w.dirs = c.take<float>(b * 3 * 4);
+  w.z = c.take<float>(b * N * 4);
+  w.feat = c.take<float>(b * kRayFeat * 4);
+  w.rgb_c = c.take<float>(b * N * 3 * 4);
+  w.sigma_c = c.take<float>(b * N * 4);
+  w.w_c = c.take<float>(b * N * 4);
+  w.z_all = c.take<float>(b * T * 4);
+  w.z_fine = c.take<float>(b * Nf * 4);
+  w.merged_src = c.take<uint16_t>((b * T + 1) / 2 * 4);
+  w.rgb_f = c.take<float>(b * Nf * 3 * 4);
+  w.sigma_f = c.take<float>(b * Nf * 4);
+  w.maps = c.take<float>(b * 4 * 4);
+  w.live = w.count = nullptr;
+  w.blocks = nullptr;
+  if (occ) {
+    const int64_t per = B * (int64_t)(N > Nf ? N : Nf);
+    w.live = c.take<int>((size_t)per * 4);
+    w.count = c.take<int>(4);
+    w.blocks = c.take<uint32_t>(occ_block_count_bytes(per));
   }
-  return at;
+  return c.at;
 }
 
-size_t nerf_render_occ_workspace_bytes(int64_t B, int N, int Nf) {
+// (one chunk's worth: the chunks of a call past the launch-size limit reuse it in stream order)
+static size_t render_workspace_bytes(int64_t B, int N, int Nf, bool occ) {
   if (B < 0 || N < 1 || Nf < 0) return 0;
   const int64_t chunk = nerf_render_chunk_rays(N, Nf);
-  size_t off[W_COUNT], off_occ[WO_COUNT_REGIONS];
-  return carve_occ(B < chunk ? B : chunk, N, Nf, off, off_occ);
+  RenderWs w;
+  return render_carve(B < chunk ? B : chunk, N, Nf, occ, nullptr, w);
 }
+size_t nerf_render_workspace_bytes(int64_t B, int N, int Nf) { return render_workspace_bytes(B, N, Nf, false); }
+size_t nerf_render_occ_workspace_bytes(int64_t B, int N, int Nf) { return render_workspace_bytes(B, N, Nf, true); }
 
-// render_rays_chunk's stage sequence with classify -> zero-fill -> gathered MLP in place of each MLP
-// launch.  Under NERF_ARITH_F32 every sample is evaluated by the f32 kernel and the classify pass
-// runs after it, zeroing the dead rows (the same result, no speed-up).
-static int render_rays_occ_chunk(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
-                                 double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
-                                 const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0,
-                                 const float* app, int64_t app_rows, const uint32_t* bits, int G, const float* lo,
-                                 const float* inv, float* rgb_map, float* depth_map, float* weights_out, float* z_out,
-                                 float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
-                                 hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  REQUIRE(packed && rays_o && rays_d && t_vals && rgb_map && depth_map && workspace,
-          "nerf_render_rays_occ: null pointer");
-  REQUIRE(Nf == 0 || u_lin, "nerf_render_rays_occ: u_lin required when Nf > 0");
-  REQUIRE(app_rows == 0 || app, "nerf_render_rays_occ: null appearance");
-  size_t off[W_COUNT], off_occ[WO_COUNT_REGIONS];
-  const size_t need = carve_occ(B, N, Nf, off, off_occ);
-  if (ws_bytes < need)
-    return set_error(NERF_ERR_WORKSPACE, "nerf_render_rays_occ: workspace %zu < %zu bytes", ws_bytes, need);
-  char* ws = (char*)workspace;
-  auto region = [&](int i) { return (float*)(ws + off[i]); };
-  float* dn = region(W_DIRS);
-  float* z = (Nf == 0 && z_out) ? z_out : region(W_Z);
-  float* feat = region(W_FEAT);
-  float* rgb_c = region(W_RGBC);
-  float* sigma_c = region(W_SIGC);
-  float* wc = (Nf == 0) ? weights_out : region(W_WC);
-  float* z_all = z_out ? z_out : region(W_ZALL);
-  float* maps = region(W_MAPS);
-  int* live = (int*)(ws + off_occ[WO_LIVE]);
-  int* count = (int*)(ws + off_occ[WO_COUNT]);
-  uint32_t* blocks = (uint32_t*)(ws + off_occ[WO_BLOCKS]);
-  const uint64_t seed_c = rng_key_at(seed, (uint64_t)ray0 * (uint64_t)N);
-  const uint64_t seed_f = rng_key_at(seed ^ 0x5DEECE66Dull, (uint64_t)ray0 * (uint64_t)Nf);
-  const bool gathered = g_mlp_arith == NERF_ARITH_F16X3;
-  // one MLP stage over the (B, n) samples at zz
-  auto masked_mlp = [&](const float* zz, int n, float* rgb, float* sigma) -> int {
+// The arguments of nerf_render_rays / nerf_render_rays_occ (a whole call's, or one ray chunk's) and the
+// occupancy entry's grid.
+struct RenderArgs {
+  const float *packed, *rays_o, *rays_d;
+  int64_t B;
+  double near, far;
+  int N, Nf;
+  const float *t_vals, *u_lin;
+  int perturb;
+  const float *t_rand, *u_rand;
+  uint64_t seed;
+  int64_t ray0;
+  const float* app;
+  int64_t app_rows;
+  float *rgb_map, *depth_map, *weights_out, *z_out, *coarse_rgb, *coarse_depth;
+  void* workspace;
+  hipStream_t s;
+};
+struct OccGrid {
+  const uint32_t* bits;
+  int G;
+  const float *lo, *inv;
+};
+
+// One ray chunk, every argument checked.  With a grid each MLP stage skips the samples outside its
+// set cells: under f16x3 classify -> zero-fill -> the gathered MLP; under NERF_ARITH_F32 every sample
+// is evaluated by the f32 kernel and the classify pass runs after it, zeroing the dead rows (the same
+// result, no speed-up).
+static int render_chunk(const RenderArgs& a, const OccGrid* grid) {
+  const int64_t B = a.B;
+  const int N = a.N, Nf = a.Nf;
+  hipStream_t s = a.s;
+  RenderWs w;
+  render_carve(B, N, Nf, grid != nullptr, a.workspace, w);
+  float* dn = w.dirs;
+  float* z = (Nf == 0 && a.z_out) ? a.z_out : w.z;
+  float* wc = (Nf == 0) ? a.weights_out : w.w_c;
+  float* z_all = a.z_out ? a.z_out : w.z_all;
+  // in-kernel draws keyed by the global ray index ray0 + r (nerf_rng_uniforms)
+  const uint64_t seed_c = rng_key_at(a.seed, (uint64_t)a.ray0 * (uint64_t)N);
+  const uint64_t seed_f = rng_key_at(a.seed ^ 0x5DEECE66Dull, (uint64_t)a.ray0 * (uint64_t)Nf);
+  // one MLP stage over the (B, n) samples at zz: the only point that looks at the grid
+  auto mlp = [&](const float* zz, int n, float* rgb, float* sigma) -> int {
+    auto dense = [&] { return launch_mlp(a.packed, a.rays_o, dn, zz, B, n, w.feat, rgb, sigma, nullptr, 0, s); };
+    if (!grid) return profiled(s, B * (int64_t)n, dense);
+    auto classify = [&] {
+      return launch_occ_classify(a.rays_o, dn, zz, B, n, grid->bits, grid->G, grid->lo, grid->inv, w.live, w.count,
+                                 nullptr, sigma, rgb, w.blocks, s);
+    };
     int rc;
-    if (gathered) {
-      if ((rc = launch_occ_classify(rays_o, dn, zz, B, n, bits, G, lo, inv, live, count, nullptr, sigma, rgb, blocks,
-                                    s)))
-        return rc;
-      return profiled_mlp_live(packed, rays_o, dn, zz, B, n, feat, rgb, sigma, live, count, s);
+    if (g_mlp_arith == NERF_ARITH_F16X3) {
+      if ((rc = classify())) return rc;
+      return profiled(s, B * (int64_t)n, [&] {
+        return launch_mlp16s_live(a.packed, a.rays_o, dn, zz, B, n, w.feat, rgb, sigma, w.live, w.count, s);
+      });
     }
-    if ((rc = profiled_mlp(packed, rays_o, dn, zz, B, n, feat, rgb, sigma, nullptr, 0, s))) return rc;
-    return launch_occ_classify(rays_o, dn, zz, B, n, bits, G, lo, inv, live, count, nullptr, sigma, rgb, blocks, s);
+    if ((rc = profiled(s, B * (int64_t)n, dense))) return rc;
+    return classify();
   };
   int rc;
-  if ((rc = launch_ray_features(packed, rays_d, B, app, app_rows, feat, s, nullptr, dn))) return rc;
-  if ((rc = launch_stratified(rays_o, dn, B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand, seed_c,
-                              z, nullptr, s)))
+  // render.py:19's normalisation in the ray-feature kernel (it writes dn)
+  if ((rc = launch_ray_features(a.packed, a.rays_d, B, a.app, a.app_rows, w.feat, s, nullptr, dn))) return rc;
+  if ((rc = launch_stratified(a.rays_o, dn, B, (float)a.near, (float)(a.far - a.near), N, a.t_vals, a.perturb,
+                              a.t_rand, seed_c, z, nullptr, s)))
+    return rc;                                                                                 // render.py:22
+  if ((rc = mlp(z, N, w.rgb_c, w.sigma_c))) return rc;                                         // :49
+  if (Nf == 0)
+    return launch_composite(w.rgb_c, w.sigma_c, z, B, N, a.rgb_map, a.depth_map, wc, s);       // render.py:56-80
+  float* crgb = a.coarse_rgb ? a.coarse_rgb : w.maps;
+  float* cdepth = a.coarse_depth ? a.coarse_depth : w.maps + 3 * B;
+  if ((rc = launch_composite(w.rgb_c, w.sigma_c, z, B, N, crgb, cdepth, wc, s))) return rc;
+  // H1 fine pass: resample + merge (each merged slot records which coarse or fine sample it holds),
+  // the MLP run on the Nf new samples only, in sample order, and the composite over all N+Nf merged
+  // samples gathering the coarse evaluations and the fine ones through the map.  (Round 3 scattered
+  // the coarse results into merged rows and the fine MLP wrote into its slots: 4.0 GB written by
+  // the resample and 24 B per fine sample by the MLP, for the same bits.)
+  if ((rc = launch_importance(nullptr, nullptr, z, wc, B, N, Nf, a.u_lin, a.u_rand, seed_f, z_all, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, w.z_fine, nullptr, s, w.merged_src)))
     return rc;
-  if ((rc = masked_mlp(z, N, rgb_c, sigma_c))) return rc;
-  if (Nf == 0) return launch_composite(rgb_c, sigma_c, z, B, N, rgb_map, depth_map, wc, s);
-  float* crgb = coarse_rgb ? coarse_rgb : maps;
-  float* cdepth = coarse_depth ? coarse_depth : maps + 3 * B;
-  if ((rc = launch_composite(rgb_c, sigma_c, z, B, N, crgb, cdepth, wc, s))) return rc;
-  float* z_fine = region(W_ZF);
-  uint16_t* msrc = (uint16_t*)region(W_SRC);
-  float* rgb_f = region(W_RGBF);
-  float* sigma_f = region(W_SIGF);
-  if ((rc = launch_importance(nullptr, nullptr, z, wc, B, N, Nf, u_lin, u_rand, seed_f, z_all, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, z_fine, nullptr, s, msrc)))
-    return rc;
-  if ((rc = masked_mlp(z_fine, Nf, rgb_f, sigma_f))) return rc;
-  return launch_composite_merged(rgb_c, sigma_c, rgb_f, sigma_f, msrc, z_all, B, N, Nf, rgb_map, depth_map,
-                                 weights_out, s);
+  if ((rc = mlp(w.z_fine, Nf, w.rgb_f, w.sigma_f))) return rc;
+  return launch_composite_merged(w.rgb_c, w.sigma_c, w.rgb_f, w.sigma_f, w.merged_src, z_all, B, N, Nf, a.rgb_map,
+                                 a.depth_map, a.weights_out, s);
+}
+
+// Both entry points: the checks, then the chunk loop.  Calls past the launch-size limit run in ray
+// chunks: every per-ray input and output advances by the chunk's first ray, the in-kernel draws stay
+// keyed by the global ray index (ray0 + c0), and each chunk carves the caller's workspace for its own
+// (smaller) B.  The checks that need B > 0 look at the first chunk, the largest.
+static int render_rays(const char* fn, const RenderArgs& a, const OccGrid* grid, size_t ws_bytes) {
+  const int64_t B = a.B;
+  const int N = a.N, Nf = a.Nf;
+  REQUIRE(B >= 0 && a.ray0 >= 0, "%s: B=%lld ray0=%lld", fn, (long long)B, (long long)a.ray0);
+  if (N < 1 || N > 4096 || Nf < 0 || N + Nf > 4096 || (Nf > 0 && (N > 256 || Nf > 1024)))
+    return set_error(NERF_ERR_UNSUPPORTED, "%s: N=%d Nf=%d outside the supported range", fn, N, Nf);
+  if (grid) {
+    REQUIRE(grid->bits && grid->lo && grid->inv, "%s: null grid", fn);
+    if (int rc = check_grid(fn, grid->G)) return rc;
+  }
+  REQUIRE(a.app_rows == 0 || a.app_rows == 1 || a.app_rows == B, "%s: app_rows=%lld with B=%lld", fn,
+          (long long)a.app_rows, (long long)B);
+  const int64_t chunk = nerf_render_chunk_rays(N, Nf);
+  if (chunk < 1)   // (N + Nf <= 4096 <= the launch limit: unreachable, but never loop on a zero step)
+    return set_error(NERF_ERR_UNSUPPORTED, "%s: N=%d Nf=%d exceed the launch limit", fn, N, Nf);
+  if (B == 0) return NERF_OK;
+  REQUIRE(a.packed && a.rays_o && a.rays_d && a.t_vals && a.rgb_map && a.depth_map && a.workspace,
+          "%s: null pointer", fn);
+  REQUIRE(Nf == 0 || a.u_lin, "%s: u_lin required when Nf > 0", fn);
+  REQUIRE(a.app_rows == 0 || a.app, "%s: null appearance", fn);
+  RenderWs sized;
+  const size_t need = render_carve(B < chunk ? B : chunk, N, Nf, grid != nullptr, nullptr, sized);
+  if (ws_bytes < need) return set_error(NERF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+  const int64_t T = Nf > 0 ? (int64_t)N + Nf : (int64_t)N;   // weights_out / z_out columns
+  const bool per_ray_app = a.app_rows > 1;
+  for (int64_t c0 = 0; c0 < B; c0 += chunk) {
+    RenderArgs c = a;
+    c.B = B - c0 < chunk ? B - c0 : chunk;
+    c.rays_o += 3 * c0;
+    c.rays_d += 3 * c0;
+    if (c.t_rand) c.t_rand += c0 * N;
+    if (c.u_rand) c.u_rand += c0 * Nf;
+    c.ray0 += c0;
+    if (per_ray_app) {
+      c.app += c0 * kAppDim;
+      c.app_rows = c.B;
+    }
+    c.rgb_map += 3 * c0;
+    c.depth_map += c0;
+    if (c.weights_out) c.weights_out += c0 * T;
+    if (c.z_out) c.z_out += c0 * T;
+    if (c.coarse_rgb) c.coarse_rgb += 3 * c0;
+    if (c.coarse_depth) c.coarse_depth += c0;
+    if (int rc = render_chunk(c, grid)) return rc;
+  }
+  return NERF_OK;
+}
+
+int nerf_render_rays(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
+                     double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
+                     const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0, const float* app,
+                     int64_t app_rows, float* rgb_map, float* depth_map, float* weights_out, float* z_out,
+                     float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
+                     nerf_stream_t stream) {
+  const RenderArgs a{packed, rays_o, rays_d, B, near, far, N, Nf, t_vals, u_lin, perturb, t_rand, u_rand, seed, ray0,
+                     app, app_rows, rgb_map, depth_map, weights_out, z_out, coarse_rgb, coarse_depth, workspace,
+                     (hipStream_t)stream};
+  return render_rays("nerf_render_rays", a, nullptr, ws_bytes);
 }
 
 int nerf_render_rays_occ(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
@@ -783,30 +745,11 @@ int nerf_render_rays_occ(const float* packed, const float* rays_o, const float* 
                          int64_t app_rows, const uint32_t* bits, int G, const float* lo, const float* inv,
                          float* rgb_map, float* depth_map, float* weights_out, float* z_out, float* coarse_rgb,
                          float* coarse_depth, void* workspace, size_t ws_bytes, nerf_stream_t stream) {
-  REQUIRE(B >= 0 && ray0 >= 0, "nerf_render_rays_occ: B=%lld ray0=%lld", (long long)B, (long long)ray0);
-  if (N < 1 || N > 4096 || Nf < 0 || N + Nf > 4096 || (Nf > 0 && (N > 256 || Nf > 1024)))
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_render_rays_occ: N=%d Nf=%d outside the supported range", N, Nf);
-  REQUIRE(bits && lo && inv, "nerf_render_rays_occ: null grid");
-  REQUIRE_GRID("nerf_render_rays_occ", G);
-  REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "nerf_render_rays_occ: app_rows=%lld with B=%lld",
-          (long long)app_rows, (long long)B);
-  const int64_t chunk = nerf_render_chunk_rays(N, Nf);
-  if (chunk < 1)
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_render_rays_occ: N=%d Nf=%d exceed the launch limit", N, Nf);
-  const int64_t T = Nf > 0 ? (int64_t)N + Nf : (int64_t)N;
-  for (int64_t c0 = 0; c0 < B; c0 += chunk) {
-    const int64_t n = B - c0 < chunk ? B - c0 : chunk;
-    const bool per_ray_app = app_rows > 1;
-    if (int rc = render_rays_occ_chunk(
-            packed, rays_o + 3 * c0, rays_d + 3 * c0, n, near, far, N, Nf, t_vals, u_lin, perturb,
-            t_rand ? t_rand + c0 * N : nullptr, u_rand ? u_rand + c0 * Nf : nullptr, seed, ray0 + c0,
-            per_ray_app ? app + c0 * kAppDim : app, per_ray_app ? n : app_rows, bits, G, lo, inv, rgb_map + 3 * c0,
-            depth_map + c0, weights_out ? weights_out + c0 * T : nullptr, z_out ? z_out + c0 * T : nullptr,
-            coarse_rgb ? coarse_rgb + 3 * c0 : nullptr, coarse_depth ? coarse_depth + c0 : nullptr, workspace,
-            ws_bytes, (hipStream_t)stream))
-      return rc;
-  }
-  return NERF_OK;
+  const RenderArgs a{packed, rays_o, rays_d, B, near, far, N, Nf, t_vals, u_lin, perturb, t_rand, u_rand, seed, ray0,
+                     app, app_rows, rgb_map, depth_map, weights_out, z_out, coarse_rgb, coarse_depth, workspace,
+                     (hipStream_t)stream};
+  const OccGrid grid{bits, G, lo, inv};
+  return render_rays("nerf_render_rays_occ", a, &grid, ws_bytes);
 }
 
 }  // extern "C"

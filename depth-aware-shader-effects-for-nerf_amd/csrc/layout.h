@@ -264,7 +264,7 @@ NERF_HD constexpr int64_t tile_col(int c) { return (int64_t)(c / 8) * 256; }
 NERF_HD constexpr int64_t tile_off(int64_t m, int f, int R) {
   return (m / 32) * 32 * (int64_t)R + (int64_t)(f / 8) * 256 + (m % 32) * 8 + f % 8;
 }
-// Block exponents (the split arithmetic's weight gradients, train.hip wgrad_h16h_kernel and
+// Block exponents (the split arithmetic's weight gradients, wgrad.hip wgrad_h16h_kernel and
 // wgrad_pair16_kernel).  The f16x3 forward and data-gradient kernels record, for each 32-sample block
 // and each weight-gradient operand, the exponent e of the block's largest |value| (max < 2^e; an
 // all-zero block e = kBlockExpZero), as the integer-valued float -(kBlockExpBias + e), in row padding:

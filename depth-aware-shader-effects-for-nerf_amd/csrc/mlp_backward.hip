@@ -2,7 +2,7 @@
 // MLP part of loss.backward(), src/train.py:90), one wave per 32 samples, mirroring the forward
 // kernels with transposed weights, and the packers of those weights (nerf_pack_weights_transposed
 // and its host twin; layout.h "transposed weights").  Each data-gradient kernel writes every layer's
-// d loss / d pre-activation to the tile-major gradient rows (layout.h kGrad*) for the weight gradients (train.hip).
+// d loss / d pre-activation to the tile-major gradient rows (layout.h kGrad*) for the weight gradients (wgrad.hip).
 //
 //   packT_kernel                  the f32 fragments of W_l^T
 //   statsT16_kernel               the split scales and the data-gradient bound constants

@@ -1,4 +1,4 @@
-// What crosses the training translation units (composite_bwd.hip, mlp_backward.hip, train.hip,
+// What crosses the training translation units (composite_bwd.hip, mlp_backward.hip, wgrad.hip,
 // adam.hip, train_api.hip): the launchers' prototypes, the host structs passed between
 // them, the weight gradients' chunk policy and workspace sizers, and the f32 MFMA wrapper.  The
 // transposed-weight layout is in layout.h; no kernel is defined here.
@@ -100,7 +100,7 @@ void packT_host(const float* const* params, float* packedT);
 int launch_mlp_backward(const float* packed, const float* packedT, const float* save, const uint32_t* masks,
                         const float* sigma, const float* rgb, const float* dsigma, const float* drgb, int64_t M,
                         float* grad, hipStream_t s, bool store_dhd = true);
-// train.hip (the weight gradients)
+// wgrad.hip (the weight gradients)
 int launch_wgrad(const float* a, int64_t lda, int N, const float* x, int64_t ldx, int K, int64_t x_div, int64_t M,
                  float* out_w, int ldo, float* out_b, int accumulate, float* ws, hipStream_t s,
                  const WgradSplit* split = nullptr, bool tiled = false, bool x_tiled = true,

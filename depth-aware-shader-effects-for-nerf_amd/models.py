@@ -7,7 +7,7 @@ draws the same weights and ``load_state_dict`` accepts the reference's checkpoin
 on weights packed once per parameter version into the MFMA fragment layout (csrc/layout.h).
 With gradients enabled and trainable parameters (or an appearance embedding that requires grad)
 the forward runs the training kernels instead and is differentiable (autograd.py): the backward
-is the MFMA data-gradient chain and weight-gradient reductions of csrc/mlp_backward.hip and csrc/train.hip.
+is the MFMA data-gradient chain and weight-gradient reductions of csrc/mlp_backward.hip and csrc/wgrad.hip.
 """
 import ctypes
 

@@ -33,7 +33,7 @@ and ``background_color``.  Keyword-only extras:
 With gradients enabled and a trainable model (or an appearance embedding that requires grad),
 the reference-compat call (coarse; hierarchical, staged and timing unset) runs the training
 kernels instead (autograd.py): rgb_map and depth_map carry a grad_fn whose backward is the
-composite backward + MLP data-gradient chain + weight-gradient reductions of csrc/composite_bwd.hip, mlp_backward.hip and train.hip, as
+composite backward + MLP data-gradient chain + weight-gradient reductions of csrc/composite_bwd.hip, mlp_backward.hip and wgrad.hip, as
 the reference's training loop needs (src/train.py:77-92).  The H1 hierarchical pass has no
 reference training semantics (render.py:83-86 is a stub): with gradients enabled and a trainable
 model it raises (RuntimeError naming hierarchical=True) instead of silently returning no graph.
@@ -111,35 +111,27 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
     if Nf:
         crgb = torch.empty(B, 3, device=dev)
         cdepth = torch.empty(B, 1, device=dev)
-    if occupancy is not None:
-        if occupancy.bits.device != dev:
-            raise ValueError(f"nerfmi.volume_render(occupancy=): the grid is on {occupancy.bits.device}, the render "
-                             f"runs on {dev}")
-        if occupancy.bits.dtype != torch.int32 or occupancy.bits.numel() != occupancy.words:
-            raise ValueError(f"nerfmi.volume_render(occupancy=): bits must be {occupancy.words} int32 words, got "
-                             f"{occupancy.bits.numel()} of {occupancy.bits.dtype}")
-        ws = torch.empty(lib.nerf_render_occ_workspace_bytes(B, N, Nf), dtype=torch.uint8, device=dev)
-        _lib.check(lib.nerf_render_rays_occ(
-            _lib.ptr(packed), _lib.ptr(o), _lib.ptr(d), B, float(near), float(far), N, Nf, _lib.ptr(t_vals),
-            _lib.ptr(u_lin), int(bool(perturb)), _lib.ptr(tr), _lib.ptr(ur), seed or 0, int(ray_offset),
-            _lib.ptr(app), rows, _lib.ptr(occupancy.bits.contiguous()), occupancy.resolution, occupancy.c_lo(),
-            occupancy.c_inv(),
-            _lib.ptr(rgb_map), _lib.ptr(depth_map), _lib.ptr(weights), _lib.ptr(z_vals),
-            _lib.ptr(crgb) if Nf else None, _lib.ptr(cdepth) if Nf else None, _lib.ptr(ws), ws.numel(),
-            _lib.stream()), "nerf_render_rays_occ")
-        if Nf:
-            cw, cz = None, None
-    elif timing is None and not staged:
-        ws = torch.empty(lib.nerf_render_workspace_bytes(B, N, Nf), dtype=torch.uint8, device=dev)
-        _lib.check(lib.nerf_render_rays(
-            _lib.ptr(packed), _lib.ptr(o), _lib.ptr(d), B, float(near), float(far), N, Nf, _lib.ptr(t_vals),
-            _lib.ptr(u_lin), int(bool(perturb)), _lib.ptr(tr), _lib.ptr(ur), seed or 0, int(ray_offset),
-            _lib.ptr(app), rows,
-            _lib.ptr(rgb_map), _lib.ptr(depth_map), _lib.ptr(weights), _lib.ptr(z_vals),
-            _lib.ptr(crgb) if Nf else None, _lib.ptr(cdepth) if Nf else None, _lib.ptr(ws), ws.numel(),
-            _lib.stream()), "nerf_render_rays")
-        if Nf:
-            cw, cz = None, None
+    if occupancy is not None or (timing is None and not staged):
+        # the single call: nerf_render_rays, or with a grid nerf_render_rays_occ (the grid's four arguments
+        # go in front of the outputs)
+        P = _lib.ptr
+        inputs = [P(packed), P(o), P(d), B, float(near), float(far), N, Nf, P(t_vals), P(u_lin), int(bool(perturb)),
+                  P(tr), P(ur), seed or 0, int(ray_offset), P(app), rows]
+        outputs = [P(rgb_map), P(depth_map), P(weights), P(z_vals), P(crgb) if Nf else None,
+                   P(cdepth) if Nf else None]
+        entry, ws_bytes = "nerf_render_rays", lib.nerf_render_workspace_bytes
+        if occupancy is not None:
+            if occupancy.bits.device != dev:
+                raise ValueError(f"nerfmi.volume_render(occupancy=): the grid is on {occupancy.bits.device}, the "
+                                 f"render runs on {dev}")
+            if occupancy.bits.dtype != torch.int32 or occupancy.bits.numel() != occupancy.words:
+                raise ValueError(f"nerfmi.volume_render(occupancy=): bits must be {occupancy.words} int32 words, got "
+                                 f"{occupancy.bits.numel()} of {occupancy.bits.dtype}")
+            inputs += [P(occupancy.bits.contiguous()), occupancy.resolution, occupancy.c_lo(), occupancy.c_inv()]
+            entry, ws_bytes = "nerf_render_rays_occ", lib.nerf_render_occ_workspace_bytes
+        ws = torch.empty(ws_bytes(B, N, Nf), dtype=torch.uint8, device=dev)
+        _lib.check(getattr(lib, entry)(*inputs, *outputs, P(ws), ws.numel(), _lib.stream()), entry)
+        cw, cz = None, None
     else:
         cw, cz = _staged(lib, packed, o, d, B, near, far, N, Nf, t_vals, u_lin, perturb, tr, ur, seed or 0,
                          int(ray_offset), app, rows, rgb_map, depth_map, weights, z_vals, crgb if Nf else None,

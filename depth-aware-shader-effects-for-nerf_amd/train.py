@@ -157,6 +157,46 @@ class Trainer:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         return self._ws
 
+    # ------------------------------------------------- what the step variants and profile_step share
+    def _batch(self, rays_o, rays_d, target):
+        """(o, d, target) as contiguous float32 (B,3) tensors on the device."""
+        return tuple(t.reshape(-1, 3).to(self.dev, torch.float32).contiguous() for t in (rays_o, rays_d, target))
+
+    def _t_vals(self, N):
+        if N not in self._tvals:
+            self._tvals[N] = linspace_table(N, self.dev)
+        return self._tvals[N]
+
+    def _app_row(self, app_idx):
+        """(app, rows): the batch's image's appearance row and 1, or (None, 0)."""
+        if self.n_images and app_idx is not None:
+            return self.appearance_embeddings[int(app_idx)].reshape(1, _APP_DIM), 1
+        return None, 0
+
+    def _maps(self, B):
+        return torch.empty(B, 3, device=self.dev), torch.empty(B, device=self.dev)
+
+    def _pack_transposed_aside(self, main):
+        """The transposed weights are read only by the backward: they are packed on a side stream while
+        the forward runs (forked after everything queued so far, so after the previous step's backward
+        read them; the caller waits for self._join before this step's backward)."""
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.dev)
+            self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
+        self._fork.record(main)
+        self._side.wait_event(self._fork)
+        _lib.check(self.lib.nerf_pack_weights_transposed(self.param_ptrs, _lib.ptr(self.packedT),
+                                                         self._side.cuda_stream), "nerf_pack_weights_transposed")
+        if self.app_grad is not None:    # the table's gradient is one row this step: zeroed beside the forward
+            with torch.cuda.stream(self._side):
+                self.app_grad.zero_()
+        self._join.record(self._side)
+
+    def _zero_unused_projection(self, rows):
+        if rows == 0:   # appearance_projection unused: its gradient is zero, as torch leaves it (None → no update)
+            self.view(self.grad, 20).zero_()
+            self.view(self.grad, 21).zero_()
+
     # ------------------------------------------------------------------------------ one step
     def forward_backward(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, seed=None, _marks=None):
         """Loss (device scalar) and gradients in self.grad for one batch (train.py:77-90).
@@ -164,9 +204,7 @@ class Trainer:
         t_rand (B,N) = the torch.rand draw of ray_utils.py:80; else the in-kernel RNG on `seed`."""
         lib, s, P = self.lib, _lib.stream(), _lib.ptr
         N = self.config.num_samples
-        o = rays_o.reshape(-1, 3).to(self.dev, torch.float32).contiguous()
-        d = rays_d.reshape(-1, 3).to(self.dev, torch.float32).contiguous()
-        tgt = target.reshape(-1, 3).to(self.dev, torch.float32).contiguous()
+        o, d, tgt = self._batch(rays_o, rays_d, target)
         B = o.shape[0]
         if t_rand is not None:
             t_rand = t_rand.to(self.dev, torch.float32).contiguous()
@@ -176,32 +214,14 @@ class Trainer:
         if self.occupancy is not None:
             return self._forward_backward_occ(o, d, tgt, app_idx, t_rand, seed, _marks)
         _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
-        # The transposed weights are read only by the backward: they are packed on a side stream while
-        # the forward runs (forked after everything queued so far, so after the previous step's
-        # backward read them; joined before this step's backward).
         main = torch.cuda.current_stream(self.dev)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.dev)
-            self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
-        self._fork.record(main)
-        self._side.wait_event(self._fork)
-        _lib.check(lib.nerf_pack_weights_transposed(self.param_ptrs, P(self.packedT), self._side.cuda_stream),
-                   "nerf_pack_weights_transposed")
-        if self.app_grad is not None:    # the table's gradient is one row this step: zeroed beside the forward
-            with torch.cuda.stream(self._side):
-                self.app_grad.zero_()
-        self._join.record(self._side)
-        if N not in self._tvals:
-            self._tvals[N] = linspace_table(N, self.dev)
+        self._pack_transposed_aside(main)
+        t_vals = self._t_vals(N)
         ws = self._workspace(B, N)
-        rgb_map = torch.empty(B, 3, device=self.dev)
-        depth = torch.empty(B, device=self.dev)
-        if self.n_images and app_idx is not None:
-            app, rows = self.appearance_embeddings[int(app_idx)].reshape(1, _APP_DIM), 1
-        else:
-            app, rows = None, 0
+        rgb_map, depth = self._maps(B)
+        app, rows = self._app_row(app_idx)
         _lib.check(lib.nerf_train_forward(P(self.packed), P(o), P(d), B, self.near, self.far, N,
-                                          P(self._tvals[N]), 1, P(t_rand), int(seed), P(app), rows, P(rgb_map),
+                                          P(t_vals), 1, P(t_rand), int(seed), P(app), rows, P(rgb_map),
                                           P(depth), None, None, P(ws), ws.numel(), s),
                    "nerf_train_forward")
         if _marks is not None:
@@ -212,9 +232,7 @@ class Trainer:
         _lib.check(lib.nerf_train_backward(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, P(app), rows,
                                            self.grad_ptrs, P(dapp), P(self.loss_buf), P(ws), ws.numel(), s),
                    "nerf_train_backward")
-        if rows == 0:   # appearance_projection unused: its gradient is zero, as torch leaves it (None → no update)
-            self.view(self.grad, 20).zero_()
-            self.view(self.grad, 21).zero_()
+        self._zero_unused_projection(rows)
         return self.loss_buf[0], rgb_map
 
     def _forward_backward_occ(self, o, d, tgt, app_idx, t_rand, seed, _marks=None):
@@ -229,36 +247,21 @@ class Trainer:
             raise ValueError(f"Trainer: the occupancy grid is on {g.device}, the trainer on {self.dev}")
         N = self.config.num_samples
         B = o.shape[0]
-        if N not in self._tvals:
-            self._tvals[N] = linspace_table(N, self.dev)
+        t_vals = self._t_vals(N)
         need = lib.nerf_train_occ_workspace_bytes(B, N)
         if self._ws_occ is None or self._ws_occ.numel() < need:
             self._ws_occ = torch.empty(need, dtype=torch.uint8, device=self.dev)
         ws = self._ws_occ
         main = torch.cuda.current_stream(self.dev)
-        _lib.check(lib.nerf_train_occ_sample(P(o), P(d), B, self.near, self.far, N, P(self._tvals[N]), 1, P(t_rand),
+        _lib.check(lib.nerf_train_occ_sample(P(o), P(d), B, self.near, self.far, N, P(t_vals), 1, P(t_rand),
                                              int(seed), P(g.bits), g.resolution, g.c_lo(), g.c_inv(),
                                              P(self._live_dev), P(ws), ws.numel(), s), "nerf_train_occ_sample")
         self._live_host.copy_(self._live_dev, non_blocking=True)
         self._live_ev.record(main)
         _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.dev)
-            self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
-        self._fork.record(main)
-        self._side.wait_event(self._fork)
-        _lib.check(lib.nerf_pack_weights_transposed(self.param_ptrs, P(self.packedT), self._side.cuda_stream),
-                   "nerf_pack_weights_transposed")
-        if self.app_grad is not None:
-            with torch.cuda.stream(self._side):
-                self.app_grad.zero_()
-        self._join.record(self._side)
-        rgb_map = torch.empty(B, 3, device=self.dev)
-        depth = torch.empty(B, device=self.dev)
-        if self.n_images and app_idx is not None:
-            app, rows = self.appearance_embeddings[int(app_idx)].reshape(1, _APP_DIM), 1
-        else:
-            app, rows = None, 0
+        self._pack_transposed_aside(main)
+        rgb_map, depth = self._maps(B)
+        app, rows = self._app_row(app_idx)
         self._live_ev.synchronize()                      # the step's one host wait
         m_live = int(self._live_host[0])
         self.live_fraction = m_live / max(1, B * N)
@@ -273,9 +276,7 @@ class Trainer:
         _lib.check(lib.nerf_train_occ_backward(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, m_live,
                                                P(app), rows, self.grad_ptrs, P(dapp), P(self.loss_buf), P(ws),
                                                ws.numel(), s), "nerf_train_occ_backward")
-        if rows == 0:
-            self.view(self.grad, 20).zero_()
-            self.view(self.grad, 21).zero_()
+        self._zero_unused_projection(rows)
         return self.loss_buf[0], rgb_map
 
     def _rebuild_occupancy(self):
@@ -292,9 +293,7 @@ class Trainer:
         lib, s, P = self.lib, _lib.stream(), _lib.ptr
         cur = torch.cuda.current_stream()
         N = self.config.num_samples
-        o = rays_o.reshape(-1, 3).to(self.dev, torch.float32).contiguous()
-        d = rays_d.reshape(-1, 3).to(self.dev, torch.float32).contiguous()
-        tgt = target.reshape(-1, 3).to(self.dev, torch.float32).contiguous()
+        o, d, tgt = self._batch(rays_o, rays_d, target)
         B = o.shape[0]
         M = B * N
         dev = self.dev
@@ -304,16 +303,14 @@ class Trainer:
         MT = _lib.tile_rows(M)                                       # tile-major save/grad rows
         save, grad = torch.empty(MT, _lib.SAVE_ROW, device=dev), torch.empty(MT, _lib.GRAD_ROW, device=dev)
         masks = torch.empty(M, _lib.MASK_ROW, dtype=torch.int32, device=dev)
-        rgb_map, depth = torch.empty(B, 3, device=dev), torch.empty(B, device=dev)
+        rgb_map, depth = self._maps(B)
         dsig, drgb, sq = torch.empty(M, device=dev), torch.empty(M, 3, device=dev), torch.empty(B, device=dev)
         grads = [torch.empty_like(self.view(self.grad, i)) for i in range(24)]
         gptr = (ctypes.c_void_p * 24)(*[g.data_ptr() for g in grads])
         wsz = self.lib.nerf_param_grads_workspace_bytes(M)
         ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
-        app, rows = (self.appearance_embeddings[int(app_idx)].reshape(1, _APP_DIM), 1) \
-            if (self.n_images and app_idx is not None) else (None, 0)
-        if N not in self._tvals:
-            self._tvals[N] = linspace_table(N, dev)
+        app, rows = self._app_row(app_idx)
+        t_vals = self._t_vals(N)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(8)]
         ck = _lib.check
         ev[0].record(cur)
@@ -322,7 +319,7 @@ class Trainer:
         ev[1].record(cur)
         ck(lib.nerf_normalize_dirs(P(d), B, P(dn), s), "normalize")
         ck(lib.nerf_sample_stratified(P(o), P(dn), B, self.near, self.far, N,
-                                      P(self._tvals[N]), 1, None, seed, P(z), None, s), "stratified")
+                                      P(t_vals), 1, None, seed, P(z), None, s), "stratified")
         ck(lib.nerf_ray_features_train(P(self.packed), P(dn), B, P(app), rows, P(feat), P(encd), s), "features")
         ev[2].record(cur)
         ck(lib.nerf_mlp_forward_train(P(self.packed), P(o), P(dn), P(z), B, N, P(feat), P(encd), P(rgb), P(sigma),

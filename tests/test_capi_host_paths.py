@@ -1,0 +1,210 @@
+"""The host layer of libnerfmi.so pinned against recordings (CPU, no launch): the exact workspace
+sizes of every carve, and the (return code, nerf_last_error()) of every argument check of the render
+and training entry points that exist with and without an occupancy grid.
+
+Both tables are recorded results (tests/golden/host_workspace_bytes.json, host_error_parity.json):
+    NERFMI_LIB=<the build to record from> python tests/test_capi_host_paths.py
+rewrites them.  Every call below passes fake non-null pointers, so each one must fail a check or hit
+its empty-batch return before anything is launched: a call that would pass every check is left out
+(see the notes in error_cases), and the test refuses a recording that holds a HIP error."""
+import ctypes
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+GOLDEN = os.path.join(REPO, "tests", "golden")
+
+RENDER_SHAPES = [(1, 1, 0), (37, 7, 0), (37, 7, 5), (256, 64, 128), (640000, 64, 128), (1 << 25, 64, 128)]
+TRAIN_SHAPES = [(1, 1), (37, 7), (100, 40), (256, 64), (4096, 64)]
+CLASSIFY_SHAPES = [(1, 1), (37, 7), (1000, 7)]
+
+
+def workspace_sizes(lib):
+    out = {}
+    for B, N, Nf in RENDER_SHAPES:
+        out[f"nerf_render_workspace_bytes({B},{N},{Nf})"] = lib.nerf_render_workspace_bytes(B, N, Nf)
+        out[f"nerf_render_occ_workspace_bytes({B},{N},{Nf})"] = lib.nerf_render_occ_workspace_bytes(B, N, Nf)
+    for B, N in TRAIN_SHAPES:
+        out[f"nerf_train_workspace_bytes({B},{N})"] = lib.nerf_train_workspace_bytes(B, N)
+        out[f"nerf_train_occ_workspace_bytes({B},{N})"] = lib.nerf_train_occ_workspace_bytes(B, N)
+        out[f"nerf_param_grads_workspace_bytes({B * N})"] = lib.nerf_param_grads_workspace_bytes(B * N)
+    for B, n in CLASSIFY_SHAPES:
+        out[f"nerf_occupancy_classify_workspace_bytes({B},{n})"] = lib.nerf_occupancy_classify_workspace_bytes(B, n)
+    return out
+
+
+P = 0x1000            # a fake device pointer: never dereferenced by a check
+B, N, NF = 4, 8, 5
+F32, F16X3 = 0, 1
+
+
+def error_cases(lib):
+    """{case name: [return code, message]}.  One valid call per entry point, one argument made bad at
+    a time.  The valid call itself is never made, and as a second guard every mutated call but the
+    ones a host table refuses also carries a workspace one byte short (nerf_param_grads: no workspace
+    at all), so a mutation that slipped past its check would end at the workspace check, not at a
+    launch.  Left out because they pass every check: null for the optional pointers (t_rand, u_rand,
+    weights_out, z_out, coarse_*, dapp); N = 4097 for nerf_mlp_forward_live (no upper bound on N);
+    the f32 setting for the entries that run under both arithmetics; B == 0 for nerf_train_occ_sample
+    (it then clears the caller's live count on the device); nerf_param_grads with a workspace one
+    byte short (it still holds both streams' partial buffers)."""
+    lo = (ctypes.c_float * 3)(-1.0, -1.0, -1.0)
+    inv = (ctypes.c_float * 3)(0.5, 0.5, 0.5)
+    grads = (ctypes.c_void_p * 24)(*([P] * 24))
+    grads_hole = (ctypes.c_void_p * 24)(*([P] * 3 + [0] + [P] * 20))
+    out = {}
+
+    def run(entry, order, base, name, **change):
+        args = dict(base, **change)
+        rc = getattr(lib, entry)(*[args[k] for k in order])
+        out[f"{entry}: {name}"] = [rc, lib.nerf_last_error().decode() if rc else ""]
+
+    def sweep(entry, order, base, required, changes, f32_only=False):
+        for p in required:
+            run(entry, order, base, f"{p} null", **{p: None})
+        for name, change in changes:
+            run(entry, order, base, name, **change)
+        if f32_only:
+            prev = lib.nerf_set_mlp_arith(F32)
+            try:
+                run(entry, order, base, "under f32")
+            finally:
+                lib.nerf_set_mlp_arith(prev)
+
+    shape = [("B = -1", dict(B=-1)), ("N = 0", dict(N=0)), ("N = 4097", dict(N=4097)), ("B = 0", dict(B=0))]
+    grid = [("G = 0", dict(G=0)), ("G = 1025", dict(G=1025))]
+    live = [("M_live = -1", dict(M_live=-1)), ("M_live = B*N + 1", dict(M_live=B * N + 1))]
+    many = ("2^32 samples", dict(B=1 << 20, N=4096))
+
+    # ---- the single-call render, without and with a grid
+    order = ["packed", "rays_o", "rays_d", "B", "near", "far", "N", "Nf", "t_vals", "u_lin", "perturb", "t_rand",
+             "u_rand", "seed", "ray0", "app", "app_rows", "rgb_map", "depth_map", "weights_out", "z_out", "coarse_rgb",
+             "coarse_depth", "workspace", "ws_bytes", "stream"]
+    base = dict(packed=P, rays_o=P, rays_d=P, B=B, near=2.0, far=6.0, N=N, Nf=NF, t_vals=P, u_lin=P, perturb=1,
+                t_rand=P, u_rand=P, seed=7, ray0=0, app=P, app_rows=1, rgb_map=P, depth_map=P, weights_out=P, z_out=P,
+                coarse_rgb=P, coarse_depth=P, workspace=P, stream=None)
+    required = ["packed", "rays_o", "rays_d", "t_vals", "u_lin", "app", "rgb_map", "depth_map", "workspace"]
+    changes = shape + [("ray0 = -1", dict(ray0=-1)), ("Nf = -1", dict(Nf=-1)), ("Nf = 1025", dict(Nf=1025)),
+                       ("N = 257 with Nf", dict(N=257)), ("app_rows = 2", dict(app_rows=2)),
+                       ("workspace one byte short", {})]
+    sweep("nerf_render_rays", order, dict(base, ws_bytes=lib.nerf_render_workspace_bytes(B, N, NF) - 1), required,
+          changes)
+    i = order.index("rgb_map")
+    order = order[:i] + ["bits", "G", "lo", "inv"] + order[i:]
+    base = dict(base, bits=P, G=16, lo=lo, inv=inv, ws_bytes=lib.nerf_render_occ_workspace_bytes(B, N, NF) - 1)
+    sweep("nerf_render_rays_occ", order, base, required + ["bits", "lo", "inv"], changes + grid)
+
+    # ---- the dense training step
+    order = ["packed", "rays_o", "rays_d", "B", "near", "far", "N", "t_vals", "perturb", "t_rand", "seed", "app",
+             "app_rows", "rgb_map", "depth_map", "weights_out", "z_out", "workspace", "ws_bytes", "stream"]
+    ws_bytes = lib.nerf_train_workspace_bytes(B, N)
+    base = dict(packed=P, rays_o=P, rays_d=P, B=B, near=2.0, far=6.0, N=N, t_vals=P, perturb=1, t_rand=P, seed=7, app=P,
+                app_rows=1, rgb_map=P, depth_map=P, weights_out=P, z_out=P, workspace=0x100000, ws_bytes=ws_bytes - 1,
+                stream=None)
+    sweep("nerf_train_forward", order, base,
+          ["packed", "rays_o", "rays_d", "t_vals", "app", "rgb_map", "depth_map", "workspace"],
+          shape + [("app_rows = 2", dict(app_rows=2)), many, ("workspace one byte short", {})])
+    order = ["packed", "packedT", "rgb_map", "target", "B", "N", "app", "app_rows", "grads", "dapp", "loss", "workspace",
+             "ws_bytes", "stream"]
+    base = dict(packed=P, packedT=P, rgb_map=P, target=P, B=B, N=N, app=P, app_rows=1, grads=grads, dapp=P, loss=P,
+                workspace=0x100000, ws_bytes=ws_bytes - 1, stream=None)
+    backward_ptrs = ["packed", "packedT", "rgb_map", "target", "app", "grads", "loss", "workspace"]
+    sweep("nerf_train_backward", order, base, backward_ptrs,
+          shape + [("app_rows = 2", dict(app_rows=2)), ("gradient 3 null", dict(grads=grads_hole)),
+                   ("workspace one byte short", {}), ("no forward wrote the workspace", dict(ws_bytes=ws_bytes))])
+
+    # ---- the training step with a grid
+    ws_bytes = lib.nerf_train_occ_workspace_bytes(B, N)
+    order = ["rays_o", "rays_d", "B", "near", "far", "N", "t_vals", "perturb", "t_rand", "seed", "bits", "G", "lo",
+             "inv", "live_count", "workspace", "ws_bytes", "stream"]
+    base = dict(rays_o=P, rays_d=P, B=B, near=2.0, far=6.0, N=N, t_vals=P, perturb=1, t_rand=P, seed=7, bits=P, G=16,
+                lo=lo, inv=inv, live_count=P, workspace=0x200000, ws_bytes=ws_bytes - 1, stream=None)
+    sweep("nerf_train_occ_sample", order, base,
+          ["rays_o", "rays_d", "t_vals", "bits", "lo", "inv", "live_count", "workspace"],
+          shape[:3] + grid + [many, ("workspace one byte short", {})])
+    order = ["packed", "rays_o", "B", "N", "M_live", "app", "app_rows", "rgb_map", "depth_map", "weights_out", "z_out",
+             "workspace", "ws_bytes", "stream"]
+    base = dict(packed=P, rays_o=P, B=B, N=N, M_live=5, app=P, app_rows=1, rgb_map=P, depth_map=P, weights_out=P,
+                z_out=P, workspace=0x200000, ws_bytes=ws_bytes - 1, stream=None)
+    occ_step = shape[:3] + [("B = 0", dict(B=0, M_live=0))] + live + [("app_rows = -1", dict(app_rows=-1)), ("app_rows = 2", dict(app_rows=2)), many,
+                               ("workspace one byte short", {})]
+    sweep("nerf_train_occ_forward", order, base, ["packed", "rays_o", "app", "rgb_map", "depth_map", "workspace"],
+          occ_step, f32_only=True)
+    order = ["packed", "packedT", "rgb_map", "target", "B", "N", "M_live", "app", "app_rows", "grads", "dapp", "loss",
+             "workspace", "ws_bytes", "stream"]
+    base = dict(packed=P, packedT=P, rgb_map=P, target=P, B=B, N=N, M_live=5, app=P, app_rows=1, grads=grads, dapp=P,
+                loss=P, workspace=0x200000, ws_bytes=ws_bytes - 1, stream=None)
+    sweep("nerf_train_occ_backward", order, base, backward_ptrs,
+          occ_step + [("gradient 3 null", dict(grads=grads_hole)),
+                      ("no forward with this M_live wrote the workspace", dict(ws_bytes=ws_bytes))], f32_only=True)
+
+    # ---- the stage entry points
+    order = ["save", "grad", "M", "N", "app", "app_rows", "packed", "grads", "dapp", "workspace", "ws_bytes", "stream"]
+    base = dict(save=P, grad=P, M=B * N, N=N, app=P, app_rows=1, packed=P, grads=grads, dapp=P, workspace=P, ws_bytes=0,
+                stream=None)
+    sweep("nerf_param_grads", order, base, ["save", "grad", "app", "packed", "grads", "workspace"],
+          [("M = -1", dict(M=-1)), ("N = 0", dict(N=0)), ("N = 4097", dict(N=4097)), ("app_rows = 2", dict(app_rows=2)),
+           ("gradient 3 null", dict(grads=grads_hole)), ("M = 0", dict(M=0)), ("no workspace", {})])
+    order = ["packed", "origins", "dirs", "z_vals", "R", "N", "ray_feat", "live", "live_count", "rgb", "sigma", "stream"]
+    base = dict(packed=P, origins=P, dirs=P, z_vals=P, R=B, N=N, ray_feat=P, live=P, live_count=P, rgb=P, sigma=P,
+                stream=None)
+    sweep("nerf_mlp_forward_live", order, base,
+          ["packed", "origins", "dirs", "z_vals", "ray_feat", "live", "live_count", "rgb", "sigma"],
+          [("R = -1", dict(R=-1)), ("N = 0", dict(N=0)), ("R = 0", dict(R=0)), ("2^34 samples", dict(R=1 << 22, N=4096))],
+          f32_only=True)
+    order = ["packed", "origins", "dirs", "z_vals", "R", "N", "ray_feat", "enc_d", "live", "M_live", "rgb", "sigma",
+             "rgb_live", "sigma_live", "save", "masks", "stream"]
+    base = dict(packed=P, origins=P, dirs=P, z_vals=P, R=B, N=N, ray_feat=P, enc_d=P, live=P, M_live=5, rgb=P, sigma=P,
+                rgb_live=P, sigma_live=P, save=P, masks=P, stream=None)
+    sweep("nerf_mlp_forward_train_live", order, base,
+          ["packed", "origins", "dirs", "z_vals", "ray_feat", "enc_d", "live", "rgb", "sigma", "rgb_live", "sigma_live",
+           "save", "masks"],
+          [("R = -1", dict(R=-1)), ("N = 0", dict(N=0)), ("N = 4097", dict(N=4097)), ("R = 0", dict(R=0, M_live=0)),
+           ("2^32 samples", dict(R=1 << 20, N=4096))] + live, f32_only=True)
+    return out
+
+
+def _golden(name):
+    with open(os.path.join(GOLDEN, name)) as f:
+        return json.load(f)
+
+
+def test_workspace_sizes_are_pinned():
+    from nerfmi import _lib
+    got = workspace_sizes(_lib.load())
+    want = _golden("host_workspace_bytes.json")
+    assert got.keys() == want.keys()
+    for k in want:
+        assert got[k] == want[k], k
+    big = "nerf_render_workspace_bytes(%d,64,128)" % (1 << 25)
+    assert 0 < want["nerf_render_workspace_bytes(640000,64,128)"] < want[big]      # past the chunk limit: one chunk's
+
+
+def test_error_parity_with_the_recording():
+    from nerfmi import _lib
+    lib = _lib.load()
+    arith = lib.nerf_get_mlp_arith()
+    got = error_cases(lib)
+    assert lib.nerf_get_mlp_arith() == arith
+    want = _golden("host_error_parity.json")
+    assert got.keys() == want.keys()
+    for k in want:
+        assert got[k] == want[k], k
+    # the recording itself: no call reached a launch, and only the empty batches succeed
+    for k, (rc, msg) in want.items():
+        assert rc != 2, k
+        assert (rc == 0) == k.endswith((": B = 0", ": R = 0", ": M = 0")), k
+    assert len(want) >= 175
+
+
+if __name__ == "__main__":
+    from nerfmi import _lib
+    lib = _lib.load()
+    for name, table in (("host_workspace_bytes.json", workspace_sizes(lib)), ("host_error_parity.json", error_cases(lib))):
+        with open(os.path.join(GOLDEN, name), "w") as f:
+            json.dump(table, f, indent=1)
+            f.write("\n")
+        print(name, len(table), "entries from", _lib.LIB_PATH)

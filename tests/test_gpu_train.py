@@ -548,7 +548,7 @@ def test_pe_columns_follow_the_arithmetic(ref_state, app_vec):
 def test_weight_gradient_small_rows_keep_relative_precision(ref_state):
     """Per-entry precision of the 256 x 256 weight gradients where one neuron's gradients and one
     activation column sit ~1e-6 (2^-20) below the rest.  Under f16x3 each operand carries one power-of-
-    two scale per 2,048-sample chunk (train.hip, h16_chunk_exps), so such a column's values keep their
+    two scale per 2,048-sample chunk (wgrad.hip, h16_chunk_exps), so such a column's values keep their
     hi part but a subnormal lo part: its products carry a relative error up to ~2^(k-39) at 2^-k of the
     chunk's maximum (2^-19 here) instead of fp32's 2^-24.  Held, per entry and relative to the entry's
     sum of |a x| (an fp32 sum's own error scale), to 1e-5 in the small row, the small column and their
