@@ -14,17 +14,7 @@
 
 namespace nerf {
 
-// the largest wgrad partial buffer over the parameter list of param_grads (one stream's)
-static size_t wgrad_stream_floats(int64_t M) {
-  const int Ks[] = {kPosEnc, kHidden, kHidden + kPosEnc, kHidden + kDirEnc, kAppDim, kDirHidden};
-  size_t m = 0;
-  for (int K : Ks) {
-    const size_t f = wgrad_workspace_floats(M, kHidden, K);
-    if (f > m) m = f;
-  }
-  return m;
-}
-// param_grads' workspace: two streams' partial buffers + the ray-sum buffers
+// param_grads' workspace: two streams' partial buffers (wgrad_stream_floats, wgrad_plan.h) + the ray-sum buffers
 static size_t max_wgrad_floats(int64_t M) {
   return 2 * ((wgrad_stream_floats(M) + 63) & ~(size_t)63) + ray_sum_floats(M) + 64;
 }
@@ -196,8 +186,12 @@ int nerf_wgrad(const float* a, int64_t lda, int N, const float* x, int64_t ldx, 
   if (ws_bytes < wgrad_workspace_floats(M, N, K) * 4)
     return set_error(NERF_ERR_WORKSPACE, "nerf_wgrad: workspace %zu < %zu bytes", ws_bytes,
                      wgrad_workspace_floats(M, N, K) * 4);
-  return launch_wgrad(a, lda, N, x, ldx, K, x_div, M, out_w, K, out_b, accumulate, (float*)workspace,
-                      (hipStream_t)stream);
+  WgradGemm j;   // row-major operands, no block exponents
+  j.a = a, j.lda = lda, j.N = N;
+  j.x = x, j.ldx = ldx, j.K = K, j.x_div = x_div;
+  j.M = M;
+  j.out_w = out_w, j.ldo = K, j.out_b = out_b, j.accumulate = accumulate;
+  return launch_wgrad(j, (float*)workspace, ws_bytes / 4, (hipStream_t)stream);
 }
 
 // Every parameter gradient of NeRF (+ the appearance rows) from the saved activations and the
@@ -244,61 +238,74 @@ static H16Meta block_exps(const float* save, const float* grad, int ja, int jx) 
 static int param_grads_jobs(const float* save, const float* grad, int64_t M, int N, const float* app, int64_t app_rows,
                             const float* packed, float* const* g, float* dapp, float* wa, float* wb, size_t wfl,
                             float* rays, hipStream_t sa, hipStream_t sb) {
-  // Job: columns [k0, k0 + K) of parameter p's weight gradient (row length ldo) from x; the bias
-  // gradient with the first column block only.  The skip layer's [h3 | enc_x] runs as a 256 x 256
-  // block (the whole-tile kernel) plus the 63 PE columns, instead of one 256 x 319 GEMM on 128 x 128
-  // tiles (416 -> ~300 us per step).
   // save and grad are tile-major rows (layout.h): a slice starting at feature c is the same layout at
-  // float offset tile_col(c).  Stream B: the K <= 64 GEMMs, layers 6-7 and the heads below.
-  // ja / jx: the block-exponent entries of a and x (layout.h; -1: none)
-  struct Job { int a; int n; int x; int K; int p; int k0; int ldo; bool bias; bool b; int ja; int jx; };
+  // float offset tile_col(c).  The skip layer's [h3 | enc_x] runs as a 256 x 256 block (the whole-tile
+  // kernel) plus the 63 PE columns, instead of one 256 x 319 GEMM on 128 x 128 tiles (416 -> ~300 us per
+  // step).  Stream B: the K <= 64 GEMMs, layers 6-7 and the heads below.
   constexpr int kSkipK = kHidden + kPosEnc;
-  const Job jobs[] = {
-      {0, kHidden, kSaveEncX, kPosEnc, 0, 0, kPosEnc, true, true, -1, -1},
-      {1 * kHidden, kHidden, save_h(0), kHidden, 2, 0, kHidden, true, false, 0, 0},
-      {2 * kHidden, kHidden, save_h(1), kHidden, 4, 0, kHidden, true, false, 1, 1},
-      {3 * kHidden, kHidden, save_h(2), kHidden, 6, 0, kHidden, true, false, 2, 2},
-      {4 * kHidden, kHidden, save_h(3), kHidden, 8, 0, kSkipK, true, false, 3, 3},                  // h3 ..
-      {4 * kHidden, kHidden, save_h(3) + kHidden, kPosEnc, 8, kHidden, kSkipK, false, true, -1, -1},  // .. | enc_x
-      {5 * kHidden, kHidden, save_h(4), kHidden, 10, 0, kHidden, true, false, 4, 4},
-      {6 * kHidden, kHidden, save_h(5), kHidden, 12, 0, kHidden, true, true, 5, 5},
-      {7 * kHidden, kHidden, save_h(6), kHidden, 14, 0, kHidden, true, true, 6, 6},
-      {kGradRgb, 3, kSaveHd, kDirHidden, P_RGB_W, 0, kDirHidden, true, false, -1, -1},
-  };
   static_assert(kSaveEncX == save_h(3) + kHidden, "the skip layer's input [h3 | enc_x] is contiguous in the save row");
+  // the check and the launch of one job, on stream B (partials wb) or A
+  auto run = [&](const WgradGemm& j, bool on_b) -> int {
+    if (wgrad_workspace_floats(j.M, j.N, j.K) > wfl) return set_error(NERF_ERR_WORKSPACE, "param_grads: workspace");
+    return launch_wgrad(j, on_b ? wb : wa, wfl, on_b ? sb : sa);
+  };
+  // n gradient columns from feature ga over K save columns from feature sx, every sample's
+  auto rows_gemm = [&](int ga, int n, int sx, int K, float* out_w, int ldo, float* out_b) {
+    WgradGemm j;
+    j.a = grad + tile_col(ga), j.lda = kGradRow, j.N = n;
+    j.x = save + tile_col(sx), j.ldx = kSaveRow, j.K = K;
+    j.M = M;
+    j.out_w = out_w, j.ldo = ldo, j.out_b = out_b;
+    j.tiled = true;
+    return j;
+  };
+  // trunk layer l >= 1: d pre_l over h_{l-1} (the skip layer: its h3 columns), both with block exponents
+  auto trunk = [&](int l) {
+    WgradGemm j = rows_gemm(l * kHidden, kHidden, save_h(l - 1), kHidden, g[2 * l], l == kSkipLayer ? kSkipK : kHidden,
+                            g[2 * l + 1]);
+    j.meta = block_exps(save, grad, l - 1, l - 1);
+    return j;
+  };
+  // d pre_l over enc_x: layer 0's weight and bias, the skip layer's PE columns
+  auto pe_cols = [&](int l) {
+    return l == 0 ? rows_gemm(0, kHidden, kSaveEncX, kPosEnc, g[0], kPosEnc, g[1])
+                  : rows_gemm(l * kHidden, kHidden, kSaveEncX, kPosEnc, g[2 * l] + kHidden, kSkipK, nullptr);
+  };
+  // the 128 columns of the row-major rows at src (per-ray or per-block gradient sums) over per-ray inputs
+  auto sums_gemm = [&](const float* src, int64_t ld, int64_t rows, const float* x, int64_t ldx, int K, int64_t x_div) {
+    WgradGemm j;
+    j.a = src, j.lda = ld, j.N = kDirHidden;
+    j.x = x, j.ldx = ldx, j.K = K, j.x_div = x_div;
+    j.M = rows;
+    return j;
+  };
   int rc;
   // layer 0 and the skip layer's PE columns (both over enc_x): one launch of the split arithmetic's
   // pair kernel; under f32 two K = 63 jobs on the f32 GEMM like every other weight gradient
   const bool pe_pair = g_mlp_arith == NERF_ARITH_F16X3;
-  if (pe_pair && (rc = launch_wgrad_pe_pair(save, grad, M, g[0], g[1], g[8], wb, wfl, sb))) return rc;
+  rc = pe_pair ? launch_wgrad_pe_pair(save, grad, M, g[0], g[1], g[8], wb, wfl, sb) : run(pe_cols(0), true);
+  if (rc) return rc;
+  for (int l = 1; l < 8; ++l) {
+    if ((rc = run(trunk(l), l >= 6))) return rc;
+    if (l == kSkipLayer && !pe_pair && (rc = run(pe_cols(l), true))) return rc;
+  }
   // fused per-ray sums (the split arithmetic's dir/density launch writes d pre_dir's 8-sample sums,
   // the rgb head's launch d hd's block sums; blocks of 32 samples lie on one ray): below, on stream B
   const bool fused = rays && fused_ray_sums(N);
-  for (const Job& j : jobs) {
-    if (pe_pair && j.K == kPosEnc) continue;            // (in the pair above)
-    if (fused && j.a == kGradRgb) continue;             // (with the per-ray sums below)
-    if (wgrad_workspace_floats(M, j.n, j.K) > wfl) return set_error(NERF_ERR_WORKSPACE, "param_grads: workspace");
-    if (j.a == kGradRgb) {   // the rgb head: the streaming kernel (3 rows)
-      if ((rc = launch_wgrad_head3(grad + tile_col(kGradRgb), save + tile_col(kSaveHd), M, g[j.p], g[j.p + 1],
-                                   j.b ? wb : wa, wfl, j.b ? sb : sa)))
-        return rc;
-      continue;
-    }
-    const H16Meta hm = block_exps(save, grad, j.ja, j.jx);
-    if ((rc = launch_wgrad(grad + tile_col(j.a), kGradRow, j.n, save + tile_col(j.x), kSaveRow, j.K, 1, M, g[j.p] + j.k0,
-                           j.ldo, j.bias ? g[j.p + 1] : nullptr, 0, j.b ? wb : wa, j.b ? sb : sa, nullptr, true, true,
-                           j.ja >= 0 ? &hm : nullptr)))
-      return rc;
-  }
+  // the rgb head: the streaming kernel (3 rows); fused, with the per-ray sums below
+  if (!fused && (rc = launch_wgrad_head3(grad + tile_col(kGradRgb), save + tile_col(kSaveHd), M, g[P_RGB_W], g[P_RGB_B], wa,
+                                         wfl, sa)))
+    return rc;
   static_assert(kGradSigma == kGradDir + kDirHidden, "the density head's gradient follows dir_linear's");
   // The appearance tail, last on stream B: appearance_projection's gradient over the d hd rows at src
   // (`rows` of them, leading dimension ld, `group` of them per ray; tiled: the gradient rows themselves)
   // with x = the ray's embedding row (broadcast when app_rows == 1; row-major), then d app.
   auto app_tail = [&](const float* src, int64_t ld, int64_t rows, int group, bool tiled) -> int {
     if (app_rows == 0) return NERF_OK;     // no appearance: the projection is unused (models.py:146)
-    if (int rc = launch_wgrad(src, ld, kDirHidden, app, kAppDim, kAppDim, app_rows == 1 ? 0 : group, rows, g[P_APP_W],
-                              kAppDim, g[P_APP_B], 0, wb, sb, nullptr, tiled, /*x_tiled=*/!tiled))
-      return rc;
+    WgradGemm j = sums_gemm(src, ld, rows, app, kAppDim, kAppDim, app_rows == 1 ? 0 : group);
+    j.out_w = g[P_APP_W], j.ldo = kAppDim, j.out_b = g[P_APP_B];
+    j.tiled = tiled, j.x_tiled = !tiled;
+    if (int rc = run(j, true)) return rc;
     if (!dapp) return NERF_OK;
     if (app_rows == 1) return launch_app_grad(g[P_APP_B], 1, 1, 1, packed, dapp, sb, false);
     return launch_app_grad(src, ld, app_rows, group, packed, dapp, sb, tiled);
@@ -318,14 +325,12 @@ static int param_grads_jobs(const float* save, const float* grad, int64_t M, int
     float* S_hd = S + ray_sum_a_floats(M);                 // fused: (M / 32) x 128
     float* E = S_hd + ray_sum_b_floats(M);                 // B x 32
     constexpr int kDirRows = 160;
-    if (wgrad_workspace_floats(M, kDirRows, kHidden) > wfl) return set_error(NERF_ERR_WORKSPACE, "param_grads: workspace");
-    const WgradSplit heads{kDirHidden, g[P_SIGMA_W], kHidden, kHidden, g[P_SIGMA_B], kDirHidden + 1};
-    H16Meta hm = block_exps(save, grad, 7, 7);
-    hm.a_cols = kDirHidden + 1;                            // d pre_dir, d sigma (rows 129.. are dropped)
-    if ((rc = launch_wgrad(grad + tile_col(kGradDir), kGradRow, kDirRows, save + tile_col(save_h(7)), kSaveRow, kHidden, 1,
-                           M, g[P_DIR_W], kHidden + kDirEnc, g[P_DIR_B], 0, wb, sb, &heads, true, true, &hm,
-                           fused ? S : nullptr)))
-      return rc;
+    WgradGemm dir = rows_gemm(kGradDir, kDirRows, save_h(7), kHidden, g[P_DIR_W], kHidden + kDirEnc, g[P_DIR_B]);
+    dir.split = WgradSplit{kDirHidden, g[P_SIGMA_W], kHidden, kHidden, g[P_SIGMA_B], kDirHidden + 1};
+    dir.meta = block_exps(save, grad, 7, 7);
+    dir.meta.a_cols = kDirHidden + 1;                      // d pre_dir, d sigma (rows 129.. are dropped)
+    dir.sums = fused ? S : nullptr;
+    if ((rc = run(dir, true))) return rc;
     if (fused) {
       const HeadSums hs{save, packed, N, S_hd, E};   // (rgb_linear's weight gradient + S_hd, E)
       if ((rc = launch_wgrad_head3(grad + tile_col(kGradRgb), save + tile_col(kSaveHd), M, g[P_RGB_W], g[P_RGB_B], wb, wfl,
@@ -337,21 +342,19 @@ static int param_grads_jobs(const float* save, const float* grad, int64_t M, int
     // dir_linear's PE_4(d) columns over the sums: fused, the M / 8 rows of 8-sample sums (row m: samples
     // 8m .. 8m+7, ray 8m / N) and d hd's M / 32 block sums; else one 256-column row per ray
     const int64_t s_ld = fused ? kDirHidden : 256, s_rows = fused ? M / 8 : B;
-    if ((rc = launch_wgrad(S, s_ld, kDirHidden, E, 32, kDirEnc, fused ? N / 8 : 1, s_rows, g[P_DIR_W] + kHidden,
-                           kHidden + kDirEnc, nullptr, 0, wb, sb)))
-      return rc;
+    WgradGemm enc = sums_gemm(S, s_ld, s_rows, E, 32, kDirEnc, fused ? N / 8 : 1);
+    enc.out_w = g[P_DIR_W] + kHidden, enc.ldo = kHidden + kDirEnc;
+    if ((rc = run(enc, true))) return rc;
     if (fused) return app_tail(S_hd, kDirHidden, M / 32, N / 32, false);
     return app_tail(S + kDirHidden, 256, B, 1, false);
   }
   // dir_linear (128 rows over [h7 | enc_d]) and the density head (1 row over h7) in one GEMM: the
   // gradient row holds [d pre_dir | d sigma], so rows 0..127 are dir_linear's gradient and row 128
   // (its first 256 columns and the bias column) the density head's: h7 is read once
-  if (wgrad_workspace_floats(M, kDirHidden + 1, kHidden + kDirEnc) > wfl)
-    return set_error(NERF_ERR_WORKSPACE, "param_grads: workspace");
-  const WgradSplit heads{kDirHidden, g[P_SIGMA_W], kHidden, kHidden, g[P_SIGMA_B]};
-  if ((rc = launch_wgrad(grad + tile_col(kGradDir), kGradRow, kDirHidden + 1, save + tile_col(save_h(7)), kSaveRow,
-                         kHidden + kDirEnc, 1, M, g[P_DIR_W], kHidden + kDirEnc, g[P_DIR_B], 0, wb, sb, &heads, true)))
-    return rc;
+  WgradGemm dir = rows_gemm(kGradDir, kDirHidden + 1, save_h(7), kHidden + kDirEnc, g[P_DIR_W], kHidden + kDirEnc,
+                            g[P_DIR_B]);
+  dir.split = WgradSplit{kDirHidden, g[P_SIGMA_W], kHidden, kHidden, g[P_SIGMA_B]};
+  if ((rc = run(dir, true))) return rc;
   return app_tail(grad + tile_col(kGradHd), kGradRow, M, N, true);
 }
 

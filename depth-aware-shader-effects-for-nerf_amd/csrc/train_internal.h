@@ -1,9 +1,10 @@
 // What crosses the training translation units (composite_bwd.hip, mlp_backward.hip, wgrad.hip,
 // adam.hip, train_api.hip): the launchers' prototypes, the host structs passed between
-// them, the weight gradients' chunk policy and workspace sizers, and the f32 MFMA wrapper.  The
-// transposed-weight layout is in layout.h; no kernel is defined here.
+// them, the weight gradients' job descriptor (their chunk policy and workspace sizers: wgrad_plan.h),
+// and the f32 MFMA wrapper.  The transposed-weight layout is in layout.h; no kernel is defined here.
 #pragma once
 #include "common.h"
+#include "wgrad_plan.h"
 
 namespace nerf {
 
@@ -14,48 +15,8 @@ __device__ __forceinline__ f32x16 mfma32t(float a, float b, f32x16 c) {
 }
 
 // ------------------------------------------------------- weight gradient: chunks and workspace
-constexpr int kWChunk = 2048;   // samples per chunk
-// Chunk length of a (N, K) weight gradient outside the split-f16 GEMMs: short enough that a 2^18-sample
-// step puts a block in every resident slot.  The 256x64-tile launches (K <= 64, N > 64: layer 0
-// and the appearance projection) hold one block per CU and have one tile: 1024-sample chunks give
-// 256 blocks instead of 128.  The 128x128-tile launches hold two blocks per CU; those with fewer
-// than 3 tiles (the sigma and rgb heads) take 1024 / 512-sample chunks.
-// (N = 160: dir_linear's 128 rows + the density head's, the tile-major training path only)
-inline bool wgrad_whole_tile(int N, int K) { return (N == 256 || N == 160) && K == 256; }
-// Whole-tile chunks of 2,048 samples (128 per 262K-sample step, half the CUs): on split-f16 the
-// launches are bound by HBM, not MFMA, and halving the chunk partials (~0.5 GB per step written and
-// read back) paid +1.7 % on the training step against 1,024-sample chunks (same-box A/B,
-// profiles/r05/ab_head3_pe_clen2k.log; under bf16x6 the 2,048-sample chunks had been 3.5 % slower).
-// (Round 6, same box: 4,096-sample whole-tile chunks -11 % on the step, 64 chunks leave CUs idle; the
-// layer-0 / skip-PE pair on 2,048-sample chunks instead of 1,024 +1.1 %, its partials halved:
-// profiles/r06/ab_train_chunks.log.)
-constexpr int kWholeClen = kWChunk, kWholeMinChunks = 128;       // whole-tile chunk length, minimum chunk count
-constexpr int kPairClen = kWChunk, kPairMinChunks = 128;          // the layer-0 / skip-PE pair's
-inline int wgrad_chunk_len_big(int N, int K) {
-  if (wgrad_whole_tile(N, K)) return kWholeClen;   // one block per chunk, 256 per step
-  if (K <= 64 && N == 2 * kHidden) return kPairClen;   // (the layer-0 / skip-PE pair)
-  if (K <= 64 && N > 64) return kWChunk / 2;       // (wgrad_bf_k64_kernel: 512-sample chunks ran the GEMM
-                                                    // 3 % faster but doubled the reduction)
-  const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
-  return tiles == 1 ? kWChunk / 4 : tiles == 2 ? kWChunk / 2 : kWChunk;
-}
-// Short GEMMs (the per-ray ones over B rows) halve the chunk down to one 16-sample stage until
-// there are >= 256 chunks: 4,096 rays in 1,024-row chunks ran 8 blocks, 80-100 us per launch.
-inline int wgrad_chunk_len(int N, int K, int64_t M) {
-  int c = wgrad_chunk_len_big(N, K);
-  const int min_chunks = wgrad_whole_tile(N, K) ? kWholeMinChunks : (K <= 64 && N == 2 * kHidden) ? kPairMinChunks : 256;
-  while (c > 16 && (M + c - 1) / c < min_chunks) c /= 2;
-  return c;
-}
-
-// (+ 4 trailing floats: the split-f16 kernel's chunk exponent, wgrad_h16w_kernel)
-NERF_HD inline int64_t wgrad_stride(int N, int K) { return ((((int64_t)N * (K + 1)) + 3) & ~(int64_t)3) + 4; }
-
-inline size_t wgrad_workspace_floats(int64_t M, int N, int K) {
-  const int clen = wgrad_chunk_len(N, K, M);   // >= the chunk count of every path of launch_wgrad
-  const int64_t chunks = (M + clen - 1) / clen;
-  return (size_t)chunks * wgrad_stride(N, K);
-}
+// (the chunk policy, the workspace sizers and the route of a launch: wgrad_plan.h)
+static_assert(kWgradArithF16x3 == NERF_ARITH_F16X3, "wgrad_plan.h's arithmetic out of sync");
 
 struct H16Meta {                      // where the block exponents of a and x are (nullable: absent)
   const float* a = nullptr;           // record of block 0; block b at + b * a_stride
@@ -71,6 +32,21 @@ struct WgradSplit {                  // rows n0 <= n < n_end of a weight gradien
   int ldo = 0, k = 0;
   float* out_b = nullptr;            // its bias gradient (the bias column), nullable
   int n_end = 1 << 30;               // rows from n_end on are dropped (padding rows of a whole-tile launch)
+};
+
+// One weight-gradient GEMM (launch_wgrad): out_w[n][k] (ld ldo) and out_b[n] (nullable) (+)= sum over the M
+// samples m of a[m][n] x[m / x_div][k] (x_div = 0: one broadcast x row) and of a[m][n].
+struct WgradGemm {
+  const float* a = nullptr; int64_t lda = 0; int N = 0;                     // M rows of N values, row length lda
+  const float* x = nullptr; int64_t ldx = 0; int K = 0; int64_t x_div = 1;  // rows of K values, row length ldx
+  int64_t M = 0;
+  float* out_w = nullptr; int ldo = 0; float* out_b = nullptr; int accumulate = 0;
+  WgradSplit split;                   // (out_w null: none)
+  H16Meta meta;                       // the block exponents of a and x for the split-f16 whole-tile kernels (absent: none)
+  // tiled: a (and x when x_div == 1 and x_tiled) are tile-major rows (layout.h) of row length lda / ldx,
+  // each pointer at its slice's tile_col: the training path (param_grads).  Otherwise row-major.
+  bool tiled = false, x_tiled = true;
+  float* sums = nullptr;              // d pre_dir's 8-sample sums (wgrad_h16h_kernel's SUMS), nullable
 };
 
 // sums (nullable): S_hd and E of the fused per-ray sums (rays of N % 32 == 0 samples), save / packed
@@ -101,10 +77,7 @@ int launch_mlp_backward(const float* packed, const float* packedT, const float* 
                         const float* sigma, const float* rgb, const float* dsigma, const float* drgb, int64_t M,
                         float* grad, hipStream_t s, bool store_dhd = true);
 // wgrad.hip (the weight gradients)
-int launch_wgrad(const float* a, int64_t lda, int N, const float* x, int64_t ldx, int K, int64_t x_div, int64_t M,
-                 float* out_w, int ldo, float* out_b, int accumulate, float* ws, hipStream_t s,
-                 const WgradSplit* split = nullptr, bool tiled = false, bool x_tiled = true,
-                 const H16Meta* meta = nullptr, float* sums = nullptr);
+int launch_wgrad(const WgradGemm& j, float* ws, size_t ws_floats, hipStream_t s);
 int launch_wgrad_head3(const float* a, const float* x, int64_t M, float* out_w, float* out_b, float* ws,
                        size_t ws_floats, hipStream_t s, const HeadSums* sums = nullptr);
 int launch_wgrad_pe_pair(const float* save, const float* grad, int64_t M, float* w0, float* b0, float* w4, float* ws,

@@ -1,10 +1,8 @@
-// Training path, the weight-gradient stage (the other stages moved to composite_bwd.hip, mlp_backward.hip,
-// adam.hip and train_api.hip; this file keeps its name so that its lines keep their history; it is
-// wgrad.hip in all but name): the parameter part of loss.backward() (src/train.py:90):
+// Training path, the weight-gradient stage: the parameter part of loss.backward() (src/train.py:90):
 // dW[n][k] = sum_m dpre[m][n] x[m][k] (+ the bias column) over the batch, chunked over samples, each
-// chunk's partial reduced in a fixed order (deterministic).  Chunk policy, workspace sizers and the
-// launchers' prototypes: train_internal.h; who launches what per parameter: train_api.hip
-// (param_grads).
+// chunk's partial reduced in a fixed order (deterministic).  Chunk policy, workspace sizers and
+// the route of a launch: wgrad_plan.h; the job descriptor and the launchers' prototypes:
+// train_internal.h; who launches what per parameter: train_api.hip (param_grads).
 //
 //   wgrad_kernel, wgrad_lds_kernel      fp32 MFMA (nerf_arith F32): unaligned fallback, LDS-staged
 //   wgrad_bf_kernel, wgrad_bf_k64_kernel  bf16x6, the split arithmetic's GEMMs outside the whole tile
@@ -25,7 +23,10 @@ namespace nerf {
 // where x'[m][k] = x[xrow(m)][k] for k < K and x'[m][K] = 1 (the bias column).  xrow(m) = m / x_div
 // (x_div = 1: a per-sample input; = N: a per-ray input; 0: one broadcast row).  Each chunk's
 // partial occupies wgrad_stride(N, K) floats (N*KP rounded up to 4, for 16-byte reduce loads, + 4).
-// A chunk is kWChunk samples or the policy's wgrad_chunk_len (train_internal.h).
+// A chunk is kWChunk samples or the policy's wgrad_chunk_len (wgrad_plan.h).
+
+// Row of a 32 x 32 MFMA accumulator tile that register g holds in lane half h (layout.h).
+__device__ __forceinline__ int acc_row(int g, int h) { return (g & 3) + 8 * (g >> 2) + 4 * h; }
 
 // Fallback (unaligned operands): one wave per 32 (n) x 64 (k') tile of one chunk, operands
 // loaded straight from global memory (A = a^T fragment: n = l&31, sample = l>>5; B = x'
@@ -65,7 +66,7 @@ wgrad_kernel(const float* __restrict__ a, int64_t lda, int N, const float* __res
   float* out = partial + (size_t)blockIdx.y * wgrad_stride(N, K);
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
-    const int row = n0 + (g & 3) + 8 * (g >> 2) + 4 * hm;
+    const int row = n0 + acc_row(g, hm);
     if (row < N) {
       if (ka < KP) out[(size_t)row * KP + ka] = acc0[g];
       if (kb < KP) out[(size_t)row * KP + kb] = acc1[g];
@@ -193,7 +194,7 @@ wgrad_lds_kernel(const float* __restrict__ a, int64_t lda, int N, const float* _
     const int kk = k0 + 64 * wk + 32 * j + c;
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-      const int nn = n0 + 64 * wn + 32 * i + (g & 3) + 8 * (g >> 2) + 4 * h;
+      const int nn = n0 + 64 * wn + 32 * i + acc_row(g, h);
       if (nn < N && kk < K) out[(size_t)nn * KP + kk] = acc[g];
     }
   };
@@ -233,6 +234,29 @@ wgrad_lds_kernel(const float* __restrict__ a, int64_t lda, int N, const float* _
 constexpr int kBfStage = 16;   // samples per stage = one MFMA k-step
 constexpr int kBfRow = 24;     // bf16 per LDS row (16 samples + pad)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// The per-stage buffer resources (the 16-sample stage at sample ms: row-major based at row ms and sized
+// to the chunk's remaining rows; tile-major based at the stage's place in its 32-sample block, up to the
+// block's end, empty past the chunk) are written out in each kernel, not shared: a forceinline
+// stage_rsrc<BLK>(base, ld, ms, live, rows_left) moved the compiler's output in every kernel that used
+// it (wgrad_bf_kernel, h16_chunk_exps' callers, wgrad_h16w_kernel, wgrad_h16h_kernel,
+// wgrad_bf_k64_kernel, wgrad_pair16_kernel: other registers and schedules, up to 33 instructions more),
+// also with the row length in bytes passed in.  The same for wgrad_bf_k64_kernel's two-value x split,
+// which split3_bf16 (eight values) does not fit.
+
+// v = p0 + p1 + p2 + O(2^-27 v) for 8 values: each part the RNE bf16 of the f32 remainder (exact)
+__device__ __forceinline__ void split3_bf16(const float (&v)[8], bf16x8& p0, bf16x8& p1, bf16x8& p2) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const __bf16 h0 = (__bf16)v[j];
+    const float r1 = v[j] - (float)h0;
+    const __bf16 h1 = (__bf16)r1;
+    const float r2 = r1 - (float)h1;
+    p0[j] = h0;
+    p1[j] = h1;
+    p2[j] = (__bf16)r2;
+  }
+}
 
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -361,16 +385,7 @@ wgrad_bf_kernel(const float* __restrict__ a, int64_t lda, int N, const float* __
   };
   auto split_store = [&](float (&v)[8], __bf16 (*dst)[kBfRow], int col, int oct, int plane_stride) {
     bf16x8 p0, p1, p2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const __bf16 h0 = (__bf16)v[j];
-      const float r1 = v[j] - (float)h0;
-      const __bf16 h1 = (__bf16)r1;
-      const float r2 = r1 - (float)h1;
-      p0[j] = h0;
-      p1[j] = h1;
-      p2[j] = (__bf16)r2;
-    }
+    split3_bf16(v, p0, p1, p2);
     *reinterpret_cast<bf16x8*>(&dst[col][8 * oct]) = p0;
     *reinterpret_cast<bf16x8*>(&dst[col + plane_stride][8 * oct]) = p1;
     *reinterpret_cast<bf16x8*>(&dst[col + 2 * plane_stride][8 * oct]) = p2;
@@ -453,7 +468,7 @@ wgrad_bf_kernel(const float* __restrict__ a, int64_t lda, int N, const float* __
       const int kk = k0 + 64 * wk + 32 * j + c;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int nn = n0 + 64 * wn + 32 * i + (g & 3) + 8 * (g >> 2) + 4 * h;
+        const int nn = n0 + 64 * wn + 32 * i + acc_row(g, h);
         if (nn < N && kk < K) out[(size_t)nn * KP + kk] = acc[i][j][g];
       }
     }
@@ -472,18 +487,6 @@ wgrad_bf_kernel(const float* __restrict__ a, int64_t lda, int N, const float* __
 // The whole-tile (256 x 256) weight gradients: the trunk layers' d pre_l over h_{l-1}, the skip
 // layer's h3 block and dir/density over h7.
 constexpr int kWT = 256;
-__device__ __forceinline__ void split3_bf16(const float (&v)[8], bf16x8& p0, bf16x8& p1, bf16x8& p2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h0 = (__bf16)v[j];
-    const float r1 = v[j] - (float)h0;
-    const __bf16 h1 = (__bf16)r1;
-    const float r2 = r1 - (float)h1;
-    p0[j] = h0;
-    p1[j] = h1;
-    p2[j] = (__bf16)r2;
-  }
-}
 // ------------------------------------------------- split-f16 ("f16x3") weight gradient, 256 columns
 // The whole-tile GEMM (a chunk's 256 x 256 weight gradient in one workgroup) on
 // v_mfma_f32_32x32x16_f16 with three products per fp32 product instead of bf16x6's six: every operand value is split as v s = hi + lo (f16 each, lo =
@@ -585,7 +588,7 @@ __device__ __forceinline__ void h16_chunk_exps(const float* __restrict__ a, int6
 }
 
 typedef _Float16 H16Stage[2][2][kWT][kBfRow];   // [buffer][hi, lo][column][sample]
-template <bool BLK, int NRT>
+// (row-major rows: nerf_wgrad's operands; the tile-major training path runs wgrad_h16h_kernel)
 __device__ __forceinline__ void h16w_chunk(const float* __restrict__ a, int64_t lda, const float* __restrict__ x,
                                            int64_t ldx, int64_t M, int clen, const H16Meta& meta,
                                            float* __restrict__ partial, int chunk, H16Stage& As, float (&wmax)[4][2]) {
@@ -594,14 +597,14 @@ __device__ __forceinline__ void h16w_chunk(const float* __restrict__ a, int64_t 
   const int tid = threadIdx.x, lane = tid & 63, wk = tid >> 6;   // wave wk: columns 64 wk ..
   const int h = lane >> 5, c = lane & 31;
   const uint32_t lda4 = (uint32_t)lda * 4u, ldx4 = (uint32_t)ldx * 4u;
-  // (NRT < 8: the columns past the kept rows are not read: an offset beyond any buffer range)
-  const uint32_t avo = tid >= 32 * NRT ? 0x80000000u : BLK ? 4u * (uint32_t)(tile_col(tid) + tid % 8) : 4u * (uint32_t)tid;
-  const uint32_t as4 = BLK ? 32u : lda4, xs4 = BLK ? 32u : ldx4;
+  // (tid < kWT always; the comparison here and at the bias store is kept from the version with fewer
+  // row tiles so that the kernel's instruction list stays as it was)
+  const uint32_t avo = tid >= kWT ? 0x80000000u : 4u * (uint32_t)tid;
   uint32_t xvo[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int xc = 64 * wk + 32 * t + c;
-    xvo[t] = BLK ? 4u * (uint32_t)(tile_col(xc) + xc % 8 + 64 * h) : (uint32_t)(8 * h) * ldx4 + 4u * (uint32_t)xc;
+    xvo[t] = (uint32_t)(8 * h) * ldx4 + 4u * (uint32_t)xc;
   }
   const uint32_t mrel_end = (uint32_t)(m1 - m0);
   float ra[4][16], rx[4][2][8];
@@ -610,21 +613,18 @@ __device__ __forceinline__ void h16w_chunk(const float* __restrict__ a, int64_t 
     constexpr int SET = decltype(set_c)::value;
     const uint32_t rel0 = (uint32_t)(kBfStage * stage) < mrel_end ? (uint32_t)(kBfStage * stage) : mrel_end;
     const int64_t ms = m0 + rel0;
-    const bool live = rel0 < mrel_end;
     const __amdgpu_buffer_rsrc_t ares = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(BLK ? a + (ms / 32) * 32 * lda + (ms % 32) * 8 : a + ms * lda), (short)0,
-        BLK ? (live ? (int)(32 * lda4 - (ms % 32) * 32) : 0) : (int)((mrel_end - rel0) * lda4), 0x00020000);
+        const_cast<float*>(a + ms * lda), (short)0, (int)((mrel_end - rel0) * lda4), 0x00020000);
     const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(BLK ? x + (ms / 32) * 32 * ldx + (ms % 32) * 8 : x + ms * ldx), (short)0,
-        BLK ? (live ? (int)(32 * ldx4 - (ms % 32) * 32) : 0) : (int)((mrel_end - rel0) * ldx4), 0x00020000);
+        const_cast<float*>(x + ms * ldx), (short)0, (int)((mrel_end - rel0) * ldx4), 0x00020000);
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      ra[SET][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ares, (int)avo, (int)(j * as4), kRowLoadAux));
+      ra[SET][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ares, (int)avo, (int)(j * lda4), kRowLoadAux));
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        rx[SET][t][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xres, (int)xvo[t], (int)(j * xs4), kRowLoadAux));
+        rx[SET][t][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xres, (int)xvo[t], (int)(j * ldx4), kRowLoadAux));
   };
   using C0 = std::integral_constant<int, 0>;
   using C1 = std::integral_constant<int, 1>;
@@ -632,7 +632,7 @@ __device__ __forceinline__ void h16w_chunk(const float* __restrict__ a, int64_t 
 
   // ---- the chunk's exponents (records, else a pass over the chunk)
   int Ea, Ex;
-  h16_chunk_exps<BLK>(a, lda, x, ldx, M, m0, m1, meta, wmax, Ea, Ex);
+  h16_chunk_exps<false>(a, lda, x, ldx, M, m0, m1, meta, wmax, Ea, Ex);
   const float sa = ldexpf(1.0f, 14 - Ea), sx = ldexpf(1.0f, 14 - Ex);
 
   h16x8 fx[2][2][2];                   // split x fragments of stages st (fx[st & 1]) and st+1: [t][hi, lo]
@@ -656,9 +656,9 @@ __device__ __forceinline__ void h16w_chunk(const float* __restrict__ a, int64_t 
       *reinterpret_cast<h16x8*>(&As[buf][1][tid][8 * o]) = lo;
     }
   };
-  f32x16 acc[NRT][2];
+  f32x16 acc[8][2];
 #pragma unroll
-  for (int i = 0; i < NRT; ++i) acc[i][0] = acc[i][1] = f32x16{};
+  for (int i = 0; i < 8; ++i) acc[i][0] = acc[i][1] = f32x16{};
   const int nstages = (int)((mrel_end + 4 * kBfStage - 1) / (4 * kBfStage)) * 4;
   load(C0{}, 0);
   load(C1{}, 1);
@@ -679,8 +679,8 @@ __device__ __forceinline__ void h16w_chunk(const float* __restrict__ a, int64_t 
 #pragma unroll
     for (int p = 0; p < 2; ++p) fa[0][p] = *reinterpret_cast<const h16x8*>(&As[FB][p][c][8 * h]);
 #pragma unroll
-    for (int i = 0; i < NRT; ++i) {
-      if (i + 1 < NRT) {
+    for (int i = 0; i < 8; ++i) {
+      if (i + 1 < 8) {
 #pragma unroll
         for (int p = 0; p < 2; ++p)
           fa[(i + 1) & 1][p] = *reinterpret_cast<const h16x8*>(&As[FB][p][32 * (i + 1) + c][8 * h]);
@@ -700,12 +700,12 @@ __device__ __forceinline__ void h16w_chunk(const float* __restrict__ a, int64_t 
     // VALU of the next stage's splits; the split's LDS writes last
     __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);         // tile 0's reads
 #pragma unroll
-    for (int i = 0; i < NRT; ++i) {
-      if (i + 1 < NRT) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // DS reads (tile i+1)
+    for (int i = 0; i < 8; ++i) {
+      if (i + 1 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // DS reads (tile i+1)
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, NRT >= 8 ? 2 : 3, 0);     // VALU
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);         // VALU
       }
     }
     __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);         // DS writes
@@ -720,27 +720,26 @@ __device__ __forceinline__ void h16w_chunk(const float* __restrict__ a, int64_t 
   // the partial at the chunk's scales; its exponent eo (true = stored 2^eo) in the partial's trailing
   // slot, applied by the reduction (a VALU unscale here would pull the accumulators out of the AGPRs)
   constexpr int KP = kWT + 1;
-  const int64_t stride = wgrad_stride(32 * NRT, kWT);
+  const int64_t stride = wgrad_stride(kWT, kWT);
   float* out = partial + (size_t)chunk * stride;
 #pragma unroll
-  for (int i = 0; i < NRT; ++i)
+  for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int kk = 64 * wk + 32 * j + c;
 #pragma unroll
-      for (int g = 0; g < 16; ++g) out[(size_t)(32 * i + (g & 3) + 8 * (g >> 2) + 4 * h) * KP + kk] = acc[i][j][g];
+      for (int g = 0; g < 16; ++g) out[(size_t)(32 * i + acc_row(g, h)) * KP + kk] = acc[i][j][g];
     }
-  if (tid < 32 * NRT) out[(size_t)tid * KP + kWT] = (float)bacc;   // (the bias column: unscaled)
+  if (tid < kWT) out[(size_t)tid * KP + kWT] = (float)bacc;   // (the bias column: unscaled)
   if (tid == 0) reinterpret_cast<int*>(out)[stride - 4] = Ea + Ex - 28;   // acc = sum (a 2^(14-Ea)) (x 2^(14-Ex))
 }
 
-template <bool BLK, int NRT = 8>
 __global__ void __launch_bounds__(256, 1)
 wgrad_h16w_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ x, int64_t ldx, int64_t M,
                   int clen, H16Meta meta, float* __restrict__ partial) {
   __shared__ __attribute__((aligned(16))) H16Stage As;
   __shared__ float wmax[4][2];
-  h16w_chunk<BLK, NRT>(a, lda, x, ldx, M, clen, meta, partial, blockIdx.x, As, wmax);
+  h16w_chunk(a, lda, x, ldx, M, clen, meta, partial, blockIdx.x, As, wmax);
 }
 
 // The same 256 x 256 GEMM (tile-major rows) with two workgroups per CU: each workgroup computes half
@@ -748,7 +747,7 @@ wgrad_h16w_kernel(const float* __restrict__ a, int64_t lda, const float* __restr
 // so the two workgroups' waves (two per SIMD) fill each other's load, split and barrier waits, which a
 // lone workgroup per CU runs in lock-step ("What bounds the phase now").  Both halves read
 // all of x: block b runs chunk (b / 16) 8 + b % 8, half (b / 8) % 2, so the halves of a chunk sit on
-// one XCD (b and b + 8) and the second read of x hits its L2.  NS raw-load sets: loads run NS - 1
+// one XCD (b and b + 8) and the second read of x hits its L2.  Three raw-load sets: loads run two
 // stages ahead; the x split runs just before its stage's MFMAs (one fragment set, not two).
 // nrows < 256 (the dir/density launch: 160): a columns from nrows on are not read (zeros) and
 // output rows from nrows on are not stored; the partial has nrows rows (wgrad_stride(nrows, 256)).
@@ -759,11 +758,11 @@ wgrad_h16w_kernel(const float* __restrict__ a, int64_t lda, const float* __restr
 // sums[(m / 8) * 128 + column], m the first of the 8 samples: the per-ray inputs' GEMMs (dir_linear's
 // PE_4(d) columns) then run over M / 8 rows of these sums instead of re-reading the gradient rows
 // (ray_sums_kernel's 256 columns per sample).
-template <int NS, bool SUMS = false>
+template <bool SUMS>
 __global__ void __launch_bounds__(256, 2)
 wgrad_h16h_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ x, int64_t ldx, int64_t M,
                   int clen, int chunks, int nrows, H16Meta meta, float* __restrict__ partial,
-                  float* __restrict__ sums = nullptr) {
+                  float* __restrict__ sums) {
   __shared__ __attribute__((aligned(16))) _Float16 As[2][2][128][kBfRow];   // [buffer][hi, lo][column][sample]
   __shared__ float wmax[4][2];
   __shared__ double bsum[128];
@@ -787,7 +786,7 @@ wgrad_h16h_kernel(const float* __restrict__ a, int64_t lda, const float* __restr
     xvo[t] = 4u * (uint32_t)(tile_col(xc) + xc % 8 + 64 * h);
   }
   const uint32_t mrel_end = (uint32_t)(m1 - m0);
-  float ra[NS][8], rx[NS][2][8];
+  float ra[3][8], rx[3][2][8];
   double bacc = 0.0;
   auto load = [&](auto set_c, int stage) __attribute__((always_inline)) {
     constexpr int SET = decltype(set_c)::value;
@@ -835,20 +834,19 @@ wgrad_h16h_kernel(const float* __restrict__ a, int64_t lda, const float* __restr
   f32x16 acc[4][2];
 #pragma unroll
   for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = f32x16{};
-  constexpr int U = NS % 2 ? 2 * NS : NS;
-  const int nstages = (int)((mrel_end + U * kBfStage - 1) / (U * kBfStage)) * U;   // (extra stages add zeros)
+  // six iterations per loop trip (3 load sets x 2 LDS buffers); the extra stages add zeros
+  const int nstages = (int)((mrel_end + 6 * kBfStage - 1) / (6 * kBfStage)) * 6;
   load(std::integral_constant<int, 0>{}, 0);
-  if constexpr (NS > 2) load(std::integral_constant<int, (NS > 2 ? 1 : 0)>{}, 1);
-  if constexpr (NS > 3) load(std::integral_constant<int, (NS > 3 ? 2 : 0)>{}, 2);
+  load(std::integral_constant<int, 1>{}, 1);
   split_a(std::integral_constant<int, 0>{}, 0, 0);
   __syncthreads();
-  // iteration st (IT = st mod U: set IT % NS, buffer IT % 2): stage st+NS-1's loads; stage st's x
+  // iteration st (IT = st mod 6: set IT % 3, buffer IT % 2): stage st+2's loads; stage st's x
   // split and MFMAs, stage st+1's a split in their shadow; barrier
   auto iteration = [&](auto it_c, int st) __attribute__((always_inline)) {
-    constexpr int IT = decltype(it_c)::value, SET = IT % NS, FB = IT & 1;
-    using Nxt = std::integral_constant<int, (IT + 1) % NS>;
-    using Ld = std::integral_constant<int, (IT + NS - 1) % NS>;
-    load(Ld{}, st + NS - 1);
+    constexpr int IT = decltype(it_c)::value, SET = IT % 3, FB = IT & 1;
+    using Nxt = std::integral_constant<int, (IT + 1) % 3>;
+    using Ld = std::integral_constant<int, (IT + 2) % 3>;
+    load(Ld{}, st + 2);
     __builtin_amdgcn_sched_barrier(0);
     h16x8 fx[2][2];
 #pragma unroll
@@ -887,13 +885,14 @@ wgrad_h16h_kernel(const float* __restrict__ a, int64_t lda, const float* __restr
     __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
     __syncthreads();
   };
-#define NERF_H_IT(I) \
-  if constexpr (I < U) iteration(std::integral_constant<int, (I < U ? I : 0)>{}, st + I);
-  for (int st = 0; st < nstages; st += U) {
-    NERF_H_IT(0) NERF_H_IT(1) NERF_H_IT(2) NERF_H_IT(3) NERF_H_IT(4) NERF_H_IT(5)
+  for (int st = 0; st < nstages; st += 6) {
+    iteration(std::integral_constant<int, 0>{}, st);
+    iteration(std::integral_constant<int, 1>{}, st + 1);
+    iteration(std::integral_constant<int, 2>{}, st + 2);
+    iteration(std::integral_constant<int, 3>{}, st + 3);
+    iteration(std::integral_constant<int, 4>{}, st + 4);
+    iteration(std::integral_constant<int, 5>{}, st + 5);
   }
-#undef NERF_H_IT
-  static_assert(NS >= 2 && NS <= 3, "1..2 stages of loads in flight");
   constexpr int KP = kWT + 1;
   const int64_t stride = wgrad_stride(nrows, kWT);
   float* out = partial + (size_t)chunk * stride;
@@ -905,7 +904,7 @@ wgrad_h16h_kernel(const float* __restrict__ a, int64_t lda, const float* __restr
         const int kk = 64 * wk + 32 * j + c;
 #pragma unroll
         for (int g = 0; g < 16; ++g)
-          out[(size_t)(128 * half + 32 * i + (g & 3) + 8 * (g >> 2) + 4 * h) * KP + kk] = acc[i][j][g];
+          out[(size_t)(128 * half + 32 * i + acc_row(g, h)) * KP + kk] = acc[i][j][g];
       }
     }
   }
@@ -929,8 +928,7 @@ template <bool BLK>   // BLK: a and x tile-major (layout.h; see wgrad_bf_kernel)
 __global__ void __launch_bounds__(512)
 wgrad_bf_k64_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ x, int64_t ldx, int K,
                     int64_t M, int clen, float* __restrict__ partial) {
-  constexpr int NW = 8;
-  constexpr int XS = 16 / NW;        // x samples per thread and stage
+  constexpr int XS = 2;              // x samples per thread and stage (16 over the 8 waves)
   __shared__ __attribute__((aligned(16))) __bf16 Xs[2][3][64][kBfRow];
   const int chunk = blockIdx.x;
   const int64_t m0 = (int64_t)chunk * clen;
@@ -969,6 +967,7 @@ wgrad_bf_k64_kernel(const float* __restrict__ a, int64_t lda, const float* __res
   };
   auto store_x = [&](auto set_c, int buf) __attribute__((always_inline)) {
     constexpr int SET = decltype(set_c)::value;
+    // (two values per thread: split3_bf16 takes eight, so the split is written out here)
     __bf16 p[3][XS];
 #pragma unroll
     for (int j = 0; j < XS; ++j) {
@@ -980,15 +979,9 @@ wgrad_bf_k64_kernel(const float* __restrict__ a, int64_t lda, const float* __res
       p[1][j] = h1;
       p[2][j] = (__bf16)(r1 - (float)h1);
     }
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      if constexpr (XS == 2) {
-        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<bf16x2*>(&Xs[buf][q][xc][2 * xp]) = bf16x2{p[q][0], p[q][1]};
-      } else {
-        Xs[buf][q][xc][xp] = p[q][0];
-      }
-    }
+    for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x2*>(&Xs[buf][q][xc][2 * xp]) = bf16x2{p[q][0], p[q][1]};
   };
   f32x16 acc[2] = {f32x16{}, f32x16{}};
   const int nstages = (int)((m1 - m0 + 2 * kBfStage - 1) / (2 * kBfStage)) * 2;   // even; the extra reads zeros
@@ -1031,13 +1024,13 @@ wgrad_bf_k64_kernel(const float* __restrict__ a, int64_t lda, const float* __res
     iteration(S1{}, st + 1);
   }
   const int KP = K + 1;
-  float* out = partial + (size_t)chunk * wgrad_stride(32 * NW, K);
+  float* out = partial + (size_t)chunk * wgrad_stride(kWT, K);
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int kk = 32 * t + c;
     if (kk < K) {
 #pragma unroll
-      for (int g = 0; g < 16; ++g) out[(size_t)(32 * w + (g & 3) + 8 * (g >> 2) + 4 * h) * KP + kk] = acc[t][g];
+      for (int g = 0; g < 16; ++g) out[(size_t)(32 * w + acc_row(g, h)) * KP + kk] = acc[t][g];
     }
   }
   // bias column: this lane summed column 32w + c over its 8 samples of every stage
@@ -1046,7 +1039,7 @@ wgrad_bf_k64_kernel(const float* __restrict__ a, int64_t lda, const float* __res
 }
 
 // Layer 0's weight gradient (d pre_0 over enc_x) and the skip layer's PE columns (d pre_4 over enc_x)
-// of the split arithmetic as one 512 x 63 GEMM on split-f16 MFMA (wgrad_bf_k64_kernel<true, 16>'s
+// of the split arithmetic as one 512 x 63 GEMM on split-f16 MFMA (wgrad_bf_k64_kernel<true>'s
 // shape with wgrad_h16h_kernel's arithmetic: three f16 products per fp32 product instead of bf16x6's
 // six, two f16 parts to split instead of three bf16 parts).  16 waves per chunk (kPairClen): wave w
 // owns output rows 32w .. 32w+31 (waves 0-7 of d pre_0, 8-15 of d pre_4; one MFMA row tile, two
@@ -1206,7 +1199,7 @@ wgrad_pair16_kernel(const float* __restrict__ grad, const float* __restrict__ sa
     const int kk = 32 * t + c;
     if (kk < kPosEnc) {
 #pragma unroll
-      for (int g = 0; g < 16; ++g) out[(size_t)(32 * w + (g & 3) + 8 * (g >> 2) + 4 * h) * KP + kk] = (acc[t][g] * u0) * u1;
+      for (int g = 0; g < 16; ++g) out[(size_t)(32 * w + acc_row(g, h)) * KP + kk] = (acc[t][g] * u0) * u1;
     }
   }
   bacc += __shfl_xor(bacc, 32);
@@ -1228,7 +1221,6 @@ wgrad_pair16_kernel(const float* __restrict__ grad, const float* __restrict__ sa
 // one ray) S_hd[b] = W_rgb^T (the block's d rgb_pre sums, in double, rounded once), and for a ray's
 // first block E[ray] = the ray's PE_4(d) (its first sample's save row).  Wave (b - b0) % 4 takes
 // block b.  (Until round 6 a separate block_head_sums_kernel read the d rgb_pre rows again.)
-constexpr int kHeadChunkBlocks = 16;   // (512 chunks per 262K-sample step: two workgroups per CU)
 template <bool SUMS = false>
 __global__ void __launch_bounds__(256)
 wgrad_head3_kernel(const float* __restrict__ a, const float* __restrict__ x, int64_t M, float* __restrict__ partial,
@@ -1320,20 +1312,19 @@ wgrad_head3_kernel(const float* __restrict__ a, const float* __restrict__ x, int
   }
 }
 
-// x_blk: x tile-major (BLK and x_div == 1); under BLK a row-major x with x_div == 1 (the appearance
-// rows of one-sample "rays") takes the generic x loader, which reads row-major rows.
+// The plan's xd1: one x row per sample in a's layout; under BLK a row-major x with x_div == 1 (the
+// appearance rows of one-sample "rays") takes the generic x loader, which reads row-major rows.
 template <int WN, int WK, bool BLK>
-static int launch_wgrad_bf(const float* a, int64_t lda, int N, const float* x, int64_t ldx, int K, int64_t x_div,
-                           bool x_blk, int64_t M, int chunks, int clen, float* ws, hipStream_t s) {
-  const int ntn = (N + 64 * WN - 1) / (64 * WN), ntk = (K + 64 * WK - 1) / (64 * WK);
+static int launch_wgrad_bf(const WgradGemm& j, const WgradPlan& p, float* ws, hipStream_t s) {
+  const int ntn = (j.N + 64 * WN - 1) / (64 * WN), ntk = (j.K + 64 * WK - 1) / (64 * WK);
   const int tiles = ntn * ntk;
-  const int blocks = ((chunks + 7) / 8) * 8 * tiles;
-  if (x_div == 1 && (!BLK || x_blk))
-    hipLaunchKernelGGL((wgrad_bf_kernel<WN, WK, true, BLK>), dim3((unsigned)blocks), dim3(256), 0, s, a, lda, N, x,
-                       ldx, K, x_div, M, ntk, tiles, chunks, clen, ws);
+  const int blocks = ((p.chunks + 7) / 8) * 8 * tiles;
+  if (p.xd1)
+    hipLaunchKernelGGL((wgrad_bf_kernel<WN, WK, true, BLK>), dim3((unsigned)blocks), dim3(256), 0, s, j.a, j.lda, j.N, j.x,
+                       j.ldx, j.K, j.x_div, j.M, ntk, tiles, p.chunks, p.clen, ws);
   else
-    hipLaunchKernelGGL((wgrad_bf_kernel<WN, WK, false, BLK>), dim3((unsigned)blocks), dim3(256), 0, s, a, lda, N, x,
-                       ldx, K, x_div, M, ntk, tiles, chunks, clen, ws);
+    hipLaunchKernelGGL((wgrad_bf_kernel<WN, WK, false, BLK>), dim3((unsigned)blocks), dim3(256), 0, s, j.a, j.lda, j.N, j.x,
+                       j.ldx, j.K, j.x_div, j.M, ntk, tiles, p.chunks, p.clen, ws);
   return check_launch("wgrad_bf_kernel");
 }
 
@@ -1437,20 +1428,19 @@ wgrad_reduce_kernel(const float* __restrict__ partial, int chunks, int N, int K,
 }
 
 template <int WN, int WK, bool BLK>
-static int launch_wgrad_lds(const float* a, int64_t lda, int N, const float* x, int64_t ldx, int K, int64_t x_div,
-                            bool x_blk, int64_t M, int chunks, float* ws, hipStream_t s) {
-  const int ntn = (N + 64 * WN - 1) / (64 * WN), ntk = (K + 64 * WK - 1) / (64 * WK);
+static int launch_wgrad_lds(const WgradGemm& j, const WgradPlan& p, float* ws, hipStream_t s) {
+  const int ntn = (j.N + 64 * WN - 1) / (64 * WN), ntk = (j.K + 64 * WK - 1) / (64 * WK);
   const int tiles = ntn * ntk;
-  const int blocks = ((chunks + 7) / 8) * 8 * tiles;
-  hipLaunchKernelGGL((wgrad_lds_kernel<WN, WK, BLK>), dim3((unsigned)blocks), dim3(256), 0, s, a, lda, N, x, ldx, K,
-                     x_div, (int)(BLK && x_blk && x_div == 1), M, ntk, tiles, chunks, ws);
+  const int blocks = ((p.chunks + 7) / 8) * 8 * tiles;
+  hipLaunchKernelGGL((wgrad_lds_kernel<WN, WK, BLK>), dim3((unsigned)blocks), dim3(256), 0, s, j.a, j.lda, j.N, j.x,
+                     j.ldx, j.K, j.x_div, (int)p.x_blk, j.M, ntk, tiles, p.chunks, ws);
   return check_launch("wgrad_lds_kernel");
 }
 
 int launch_wgrad_head3(const float* a, const float* x, int64_t M, float* out_w, float* out_b, float* ws,
                        size_t ws_floats, hipStream_t s, const HeadSums* sums) {
   if (M == 0) return NERF_OK;
-  const int chunks = (int)(((M + 31) / 32 + kHeadChunkBlocks - 1) / kHeadChunkBlocks);
+  const int chunks = wgrad_head3_chunks(M);
   if ((size_t)chunks * wgrad_stride(3, kDirHidden) > ws_floats) return set_error(NERF_ERR_WORKSPACE, "wgrad_head3: workspace");
   if (sums)
     hipLaunchKernelGGL(wgrad_head3_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, s, a, x, M, ws, sums->save,
@@ -1470,8 +1460,7 @@ int launch_wgrad_head3(const float* a, const float* x, int64_t M, float* out_w, 
 int launch_wgrad_pe_pair(const float* save, const float* grad, int64_t M, float* w0, float* b0, float* w4, float* ws,
                          size_t ws_floats, hipStream_t s) {
   if (M == 0) return NERF_OK;
-  const int clen = wgrad_chunk_len(2 * kHidden, kPosEnc, M);
-  const int chunks = (int)((M + clen - 1) / clen);
+  const int clen = wgrad_pair_clen(M), chunks = wgrad_pair_chunks(M);
   if ((size_t)chunks * wgrad_stride(2 * kHidden, kPosEnc) > ws_floats)
     return set_error(NERF_ERR_WORKSPACE, "wgrad pe pair: workspace");
   hipLaunchKernelGGL(wgrad_pair16_kernel, dim3((unsigned)chunks), dim3(64 * kPairWaves), 0, s, grad, save, M, clen, ws);
@@ -1483,77 +1472,68 @@ int launch_wgrad_pe_pair(const float* save, const float* grad, int64_t M, float*
   return check_launch("wgrad_reduce_kernel");
 }
 
-// tiled: a (and x when x_div == 1 and x_tiled) are tile-major rows (layout.h) of row length lda / ldx,
-// each pointer at its slice's tile_col; the training path (param_grads).  Otherwise row-major.  The
-// appearance projection's x (the embedding rows, one per ray) is row-major: x_tiled = false.
-// meta: the block exponents of a and x (layout.h) for the split-f16 whole-tile kernel (nullable).
-int launch_wgrad(const float* a, int64_t lda, int N, const float* x, int64_t ldx, int K, int64_t x_div, int64_t M,
-                 float* out_w, int ldo, float* out_b, int accumulate, float* ws, hipStream_t s,
-                 const WgradSplit* split, bool tiled, bool x_tiled, const H16Meta* meta, float* sums) {
-  const H16Meta hm = meta ? *meta : H16Meta{};
-  if (M == 0) return NERF_OK;
-  const int KP = K + 1;
-  int chunks = (int)((M + kWChunk - 1) / kWChunk);
+// One weight-gradient GEMM (WgradGemm, train_internal.h): the route, the chunks and the reduction's
+// mode are wgrad_plan's (wgrad_plan.h), from the shape and the arithmetic in force; here the one launch
+// the plan names, then the chunk reduction.
+int launch_wgrad(const WgradGemm& j, float* ws, size_t ws_floats, hipStream_t s) {
+  if (j.M == 0) return NERF_OK;
+  const float *a = j.a, *x = j.x;
+  const int64_t lda = j.lda, ldx = j.ldx, x_div = j.x_div, M = j.M;
+  const int N = j.N, K = j.K;
   const bool aligned = ((uintptr_t)a % 16 == 0) && ((uintptr_t)x % 16 == 0) && lda % 4 == 0 && ldx % 4 == 0;
-  if (tiled && !(aligned && lda % 8 == 0 && (x_div != 1 || ldx % 8 == 0)))
+  if (j.tiled && !(aligned && lda % 8 == 0 && (x_div != 1 || ldx % 8 == 0)))
     return set_error(NERF_ERR_BAD_ARG, "wgrad: tile-major operands must be aligned with row lengths % 8 == 0");
-  const bool x_blk = tiled && x_tiled && x_div == 1;   // x tile-major
+  const WgradPlan p = wgrad_plan(g_mlp_arith, N, K, x_div, M, lda, ldx, aligned, j.tiled, j.x_tiled);
+  if (p.partial_floats > ws_floats) return set_error(NERF_ERR_WORKSPACE, "wgrad: workspace");
+  const int chunks = p.chunks, clen = p.clen;
   int rc;
-  bool sums_done = false;                               // (sums: written by the h16h launch only)
-  bool scaled = false;                                  // partials of wgrad_h16w_kernel (chunk exponents)
-  // the split arithmetic (buffer offsets of a chunk's rows must stay below 2^31): the whole-tile
-  // GEMMs on split-f16 MFMA, the rest on bf16x6
-  if (g_mlp_arith == NERF_ARITH_F16X3 && K >= 1 && lda < (1 << 18) && ldx < (1 << 18)) {
-    const int clen = wgrad_chunk_len(N, K, M);
-    chunks = (int)((M + clen - 1) / clen);
-    if (wgrad_whole_tile(N, K) && x_div == 1 && tiled && x_blk) {
-      // tile-major rows (the training path): two workgroups per CU, half the rows each; the
-      // dir_linear + density launch (N = 160) keeps 160 of 256 rows
-      if (sums)   // (the dir/density launch also writes d pre_dir's 8-sample sums, wgrad_h16h_kernel)
-        hipLaunchKernelGGL((wgrad_h16h_kernel<3, true>), dim3((unsigned)((chunks + 7) / 8 * 16)), dim3(256), 0, s, a, lda,
-                           x, ldx, M, clen, chunks, N, hm, ws, sums);
+  switch (p.route) {
+    case WgradRoute::H16Half:
+      if (j.sums)   // (the dir/density launch also writes d pre_dir's 8-sample sums)
+        hipLaunchKernelGGL(wgrad_h16h_kernel<true>, dim3((unsigned)((chunks + 7) / 8 * 16)), dim3(256), 0, s, a, lda, x,
+                           ldx, M, clen, chunks, N, j.meta, ws, j.sums);
       else
-        hipLaunchKernelGGL(wgrad_h16h_kernel<3>, dim3((unsigned)((chunks + 7) / 8 * 16)), dim3(256), 0, s, a, lda, x, ldx,
-                           M, clen, chunks, N, hm, ws, nullptr);
+        hipLaunchKernelGGL(wgrad_h16h_kernel<false>, dim3((unsigned)((chunks + 7) / 8 * 16)), dim3(256), 0, s, a, lda, x,
+                           ldx, M, clen, chunks, N, j.meta, ws, nullptr);
       rc = check_launch("wgrad_h16h_kernel");
-      scaled = true;
-      sums_done = true;
-    } else if (N == kWT && wgrad_whole_tile(N, K) && x_div == 1 && !tiled) {   // nerf_wgrad's row-major operands
-      hipLaunchKernelGGL(wgrad_h16w_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, s, a, lda, x, ldx, M, clen, hm, ws);
+      break;
+    case WgradRoute::H16Whole:
+      hipLaunchKernelGGL(wgrad_h16w_kernel, dim3((unsigned)chunks), dim3(256), 0, s, a, lda, x, ldx, M, clen, j.meta, ws);
       rc = check_launch("wgrad_h16w_kernel");
-      scaled = true;
-    } else if (N == kWT && K <= 64 && x_div == 1 && (!tiled || x_blk)) {
-      if (tiled)
+      break;
+    case WgradRoute::BfK64:
+      if (j.tiled)
         hipLaunchKernelGGL(wgrad_bf_k64_kernel<true>, dim3((unsigned)chunks), dim3(512), 0, s, a, lda, x, ldx, K, M,
                            clen, ws);
       else
         hipLaunchKernelGGL(wgrad_bf_k64_kernel<false>, dim3((unsigned)chunks), dim3(512), 0, s, a, lda, x, ldx, K, M,
                            clen, ws);
       rc = check_launch("wgrad_bf_k64_kernel");
-    } else if (K <= 64 && N > 64) {
-      rc = tiled ? launch_wgrad_bf<4, 1, true>(a, lda, N, x, ldx, K, x_div, x_blk, M, chunks, clen, ws, s)
-                 : launch_wgrad_bf<4, 1, false>(a, lda, N, x, ldx, K, x_div, x_blk, M, chunks, clen, ws, s);
-    } else {
-      rc = tiled ? launch_wgrad_bf<2, 2, true>(a, lda, N, x, ldx, K, x_div, x_blk, M, chunks, clen, ws, s)
-                 : launch_wgrad_bf<2, 2, false>(a, lda, N, x, ldx, K, x_div, x_blk, M, chunks, clen, ws, s);
+      break;
+    case WgradRoute::Bf256x64:
+      rc = j.tiled ? launch_wgrad_bf<4, 1, true>(j, p, ws, s) : launch_wgrad_bf<4, 1, false>(j, p, ws, s);
+      break;
+    case WgradRoute::Bf128x128:
+      rc = j.tiled ? launch_wgrad_bf<2, 2, true>(j, p, ws, s) : launch_wgrad_bf<2, 2, false>(j, p, ws, s);
+      break;
+    case WgradRoute::Lds256x64:
+      rc = j.tiled ? launch_wgrad_lds<4, 1, true>(j, p, ws, s) : launch_wgrad_lds<4, 1, false>(j, p, ws, s);
+      break;
+    case WgradRoute::Lds128x128:
+      rc = j.tiled ? launch_wgrad_lds<2, 2, true>(j, p, ws, s) : launch_wgrad_lds<2, 2, false>(j, p, ws, s);
+      break;
+    default: {   // WgradRoute::Fallback
+      const int tiles = ((N + 31) / 32) * ((K + 1 + 63) / 64);
+      hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)((tiles + 3) / 4), (unsigned)chunks), dim3(256), 0, s, a, lda, N,
+                         x, ldx, K, x_div, M, ws);
+      rc = check_launch("wgrad_kernel");
     }
-  } else if (aligned && K >= 1 && K <= 64 && N > 64) {
-    rc = tiled ? launch_wgrad_lds<4, 1, true>(a, lda, N, x, ldx, K, x_div, x_blk, M, chunks, ws, s)
-               : launch_wgrad_lds<4, 1, false>(a, lda, N, x, ldx, K, x_div, x_blk, M, chunks, ws, s);
-  } else if (aligned && K >= 1) {
-    rc = tiled ? launch_wgrad_lds<2, 2, true>(a, lda, N, x, ldx, K, x_div, x_blk, M, chunks, ws, s)
-               : launch_wgrad_lds<2, 2, false>(a, lda, N, x, ldx, K, x_div, x_blk, M, chunks, ws, s);
-  } else {
-    const int tiles = ((N + 31) / 32) * ((KP + 63) / 64);
-    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)((tiles + 3) / 4), (unsigned)chunks), dim3(256), 0, s, a, lda, N,
-                       x, ldx, K, x_div, M, ws);
-    rc = check_launch("wgrad_kernel");
   }
   if (rc) return rc;
-  if (sums && !sums_done) return set_error(NERF_ERR_BAD_ARG, "wgrad: 8-sample sums need the split-f16 whole-tile launch");
+  if (j.sums && !p.writes_sums) return set_error(NERF_ERR_BAD_ARG, "wgrad: 8-sample sums need the split-f16 whole-tile launch");
   const int64_t cols4 = wgrad_stride(N, K) / 4;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((cols4 + 63) / 64)), dim3(64 * kRedParts), 0, s, ws, chunks, N, K,
-                     out_w, ldo, out_b, accumulate, split ? *split : WgradSplit{}, (int)scaled);
+                     j.out_w, j.ldo, j.out_b, j.accumulate, j.split, (int)p.scaled);
   return check_launch("wgrad_reduce_kernel");
 }
 

@@ -707,7 +707,10 @@ def test_wgrad_generic_shapes():
                             (262144, 256, 256, 1), (262144, 256, 63, 1), (262144, 3, 128, 1),
                             (262144, 128, 32, 64), (262147, 1, 256, 1),
                             # 3 tiles of 128 x 128 (the dir layer): slot-filling chunk length
-                            (262144, 128, 288, 1), (50000, 128, 288, 1)]:
+                            (262144, 128, 288, 1), (50000, 128, 288, 1),
+                            # 256 x 64 tiles on aligned row-major rows with one x row per sample (lda 128, ldx 64);
+                            # the shortest chunk, two and a half stages
+                            (100, 125, 62, 1), (40, 125, 62, 1)]:
         a = torch.randn(M, N + 3, generator=g)
         xr = 1 if xdiv == 0 else (M + xdiv - 1) // xdiv if xdiv > 1 else M
         x = torch.randn(xr, K + 2, generator=g)
