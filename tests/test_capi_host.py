@@ -500,9 +500,11 @@ def test_emulated_backward_matches_autograd(ref_state, app_vec):
 
 def test_pe_sin_accuracy(tmp_path):
     """csrc/pe_sin.h (the f16x3 MLP's positional-encoding sin/cos) built for the host and compared
-    with double-precision sin/cos at the arguments the encoding forms, 2^i x for |x| < 8, i < 10:
-    within 1.6e-7 absolute (torch's float sin/cos sit within ~6e-8 of the same reference; the
-    parity tolerance on the encoding is 2e-6)."""
+    with double-precision sin/cos over the header's whole documented range: the arguments the encoding
+    forms, 2^i x for |x| < 16, i < 10 (so |a| reaches kPeSinMax = 8192, the largest argument the kernels
+    hand it), and the edge arguments +-8192, the float below 8192 and 8191.5: within 1.6e-7 absolute
+    (measured 9.3e-8; torch's float sin/cos sit within ~6e-8 of the same reference; the parity
+    tolerance on the encoding is 2e-6)."""
     import shutil
     import subprocess
     if shutil.which("g++") is None:
@@ -515,16 +517,22 @@ def test_pe_sin_accuracy(tmp_path):
 int main() {
   unsigned s = 12345u;
   double worst = 0;
+  auto measure = [&](float a) {
+    for (int h = 0; h < 2; ++h) {
+      const double ref = h ? cos((double)a) : sin((double)a);
+      const double e = fabs((double)nerf::pe_sin_reduced(a, h) - ref);
+      if (e > worst) worst = e;
+    }
+  };
   for (int n = 0; n < 400000; ++n) {
     s = s * 1664525u + 1013904223u;
-    const float x = ((s >> 8) / 16777216.0f) * 16.0f - 8.0f;
-    for (int i = 0; i < 10; ++i)
-      for (int h = 0; h < 2; ++h) {
-        const float a = x * (float)(1 << i);
-        const double ref = h ? cos((double)a) : sin((double)a);
-        const double e = fabs((double)nerf::pe_sin_reduced(a, h) - ref);
-        if (e > worst) worst = e;
-      }
+    const float x = ((s >> 8) / 16777216.0f) * 32.0f - 16.0f;
+    for (int i = 0; i < 10; ++i) measure(x * (float)(1 << i));
+  }
+  const float edges[] = {nerf::kPeSinMax, nextafterf(nerf::kPeSinMax, 0.0f), 8191.5f};
+  for (float a : edges) {
+    measure(a);
+    measure(-a);
   }
   printf("%.6g\n", worst);
   return 0;

@@ -96,6 +96,15 @@ def test_stratified_bit_exact(nerfmi_mod, golden):
 def test_positional_encoding(nerfmi_mod):
     torch.manual_seed(4)
     x = torch.randn(4096, 3) * 3
+    # values beyond the MLP kernels' fast sin/cos range (|x| > 16, csrc/pe_sin.h) and a few at +-1000, in
+    # every coordinate and both signs: this module takes the library sinf / cosf whatever the size
+    u = torch.rand(96)
+    rows, sign = torch.arange(96), 1.0 - 2.0 * ((torch.arange(96) // 3) % 2)
+    x[rows, rows % 3] = sign * (16 + 48 * u)
+    x[torch.arange(96, 102), torch.arange(6) % 3] = torch.tensor([1000.0, 1000.0, 1000.0, -1000.0, -1000.0, -1000.0])
+    for c in range(3):
+        assert bool((x[:, c] == 1000.0).any()) and bool((x[:, c] == -1000.0).any())
+        assert bool((x[:96, c] > 16).any()) and bool((x[:96, c] < -16).any())
     for levels, inc in ((10, True), (4, True), (6, False)):
         pe = nerfmi_mod.PositionalEncoding(levels, include_input=inc)
         got = pe(x.cuda())

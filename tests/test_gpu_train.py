@@ -216,22 +216,27 @@ def check_mask_words(sv, mk):
                         assert np.array_equal(got, act[:, 32 * T + 8 * q + 4 * hh + e]), (w0, hh, T, q, e)
 
 
-def _draw(R, N, seed):
-    """Random rays (o, d, sorted z in [2, 6]) and upstream gradients of their R*N samples."""
+def _draw(R, N, seed, place=None):
+    """Random rays (o, d, sorted z in [2, 6]) and upstream gradients of their R*N samples.  place:
+    (o, d, z) -> (o, d, z), moves rays after the draw (test_gpu_pe_range.py: per-ray origin offsets
+    that put samples beyond the fast sin/cos range); the random stream is the same with and without."""
     g = torch.Generator().manual_seed(seed)
     o = torch.randn(R, 3, generator=g) * 0.3
     d = F.normalize(torch.randn(R, 3, generator=g), dim=-1)
     z = torch.sort(2 + 4 * torch.rand(R, N, generator=g), dim=-1).values
+    if place is not None:
+        o, d, z = place(o, d, z)
     return o, d, z, torch.randn(R * N, 3, generator=g), torch.randn(R * N, generator=g)
 
 
-def _safe_draw(state, app, R, N, seed, rel=1e-5):
+def _safe_draw(state, app, R, N, seed, rel=1e-5, place=None):
     """_draw, keeping only rays none of whose float64 ReLU pre-activations lies within rel x (that
     layer's rms) of the kink: there an fp32 evaluation may land on either side (the CPU's and the
     GPU's roundings differ by host), which moves that sample's whole gradient chain and makes a
-    tensor's error a lottery instead of a measurement."""
+    tensor's error a lottery instead of a measurement.  place (see _draw) moves the candidates before
+    the filter, so the rays kept are clear of the kinks where they end up."""
     K = 8 * R                       # candidates (a 64-sample ray clears every kink ~1 time in 4)
-    o, d, z, gr, gs = _draw(K, N, seed)
+    o, d, z, gr, gs = _draw(K, N, seed, place)
     pts = (o[:, None, :] + d[:, None, :] * z[..., None]).reshape(-1, 3)
     dexp = d[:, None, :].expand(K, N, 3).reshape(-1, 3)
     a = None if app is None else (app.double() if app.dim() == 1 else None)
@@ -306,6 +311,11 @@ def _mlp_forward_backward(state, app, R=96, N=11, seed=3, draw=None):
 def test_forward_saves_are_the_activations(ref_state, app_vec, with_app, N):
     """N = 64: a wave's 32 samples share one ray (the f16x3 kernel's LDS feature path)."""
     r = _mlp_forward_backward(ref_state, app_vec if with_app else None, R=40 if N == 64 else 96, N=N)
+    saves_are_the_activations(r, N)
+
+
+def saves_are_the_activations(r, N):
+    """The checks of test_forward_saves_are_the_activations on a result of _mlp_forward_backward."""
     np.testing.assert_allclose(r["rgb"].numpy(), r["rgb_o"].numpy(), rtol=1e-4, atol=1e-6)
     save = r["save"].numpy()
     offs = [0, 256, 512, 768, 1088, 1344, 1600, 1856]
@@ -458,15 +468,20 @@ def test_mlp_backward_matches_autograd(ref_state, app_vec, with_app):
     R, N = 96, 11
     draw = _draw(R, N, 3)
     r = _mlp_forward_backward(ref_state, app, R=R, N=N, draw=draw)
+    data_grads_match_autograd(ref_state, app, r, draw, f"data gradients, app={with_app}")
+
+
+def data_grads_match_autograd(ref_state, app, r, draw, name):
+    """The check of test_mlp_backward_matches_autograd on a result r of _mlp_forward_backward(draw=draw)."""
     g_rgb, g_sigma = draw[3], draw[4]
-    save, M = r["save"].numpy(), R * N
+    save, M = r["save"].numpy(), draw[2].numel()
     offs = [0, 256, 512, 768, 1088, 1344, 1600, 1856]
     m_gpu = [torch.from_numpy(save[:, o:o + 256] > 0) for o in offs]
     m_gpu += [(r["sigma"] > 0).reshape(M, 1), torch.from_numpy(save[:, 2144:2272] > 0)]
     m_cpu, pre64 = [], []
     d32 = _data_grads(ref_state, r, app, g_rgb, g_sigma, torch.float32, record=m_cpu)
     d64_cpu = _data_grads(ref_state, r, app, g_rgb, g_sigma, torch.float64, masks=m_cpu, pre_out=pre64)
-    assert_branch_flips_bounded(m_cpu, m_gpu, pre64, f"data gradients, app={with_app}")
+    assert_branch_flips_bounded(m_cpu, m_gpu, pre64, name)
     d64_gpu = _data_grads(ref_state, r, app, g_rgb, g_sigma, torch.float64, masks=m_gpu)
     grad = r["grad"].numpy()
     for l in range(8):
@@ -648,13 +663,18 @@ def test_param_grads_ray_path(ref_state, app_vec, app_kind, N):
     rgb head launch's d hd block sums, wgrad_head3_kernel<true>; N = 32: one ray per 32-sample block).
     Against the oracle's float64 autograd, and two calls bit-identical (fixed-order reductions on both
     streams)."""
-    L = _lib()
-    lib, dev = L.load(), L.device()
     R = 48
     app = {"broadcast": app_vec, "per_ray": torch.randn(R, 32, generator=torch.Generator().manual_seed(5)),
            "none": None}[app_kind]
     draw = _safe_draw(ref_state, app, R, N, seed=3)
     r = _mlp_forward_backward(ref_state, app, R=R, N=N, draw=draw)
+    param_grads_ray_path(ref_state, app, app_kind, R, N, draw, r)
+
+
+def param_grads_ray_path(ref_state, app, app_kind, R, N, draw, r):
+    """The checks of test_param_grads_ray_path on a result r of _mlp_forward_backward(draw=draw)."""
+    L = _lib()
+    lib, dev = L.load(), L.device()
     save, grad = r["save_tiled"].to(dev), r["grad_tiled"].to(dev)
     packed, _, ts = packed_of(ref_state, dev)
     M = R * N
@@ -683,6 +703,7 @@ def test_param_grads_ray_path(ref_state, app_vec, app_kind, N):
             continue
         exp = r["st64"][k].grad.numpy()
         e_gpu, e_cpu = rel_l2(gt.numpy(), exp), rel_l2(g32[k], exp)
+        print(f"{k}: rel-L2 vs float64  gpu {e_gpu:.3g}  cpu fp32 {e_cpu:.3g}")
         assert e_gpu < max(2e-4, 2 * e_cpu), (k, e_gpu, e_cpu)
     if rows:
         # d app_row(r) = W_app^T sum over the ray's samples of d hd (broadcast: over all samples)
