@@ -139,6 +139,18 @@ _SIGNATURES = {
                                                ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V]),
     "nerf_mlp_forward_train_live": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V, _I64, _V, _V, _V,
                                                    _V, _V, _V, _V]),
+    # training with the hierarchical fine pass (include/nerfmi_train.h)
+    "nerf_train_hier_workspace_bytes": (ctypes.c_size_t, [_I64, ctypes.c_int, ctypes.c_int]),
+    "nerf_train_hier_forward": (ctypes.c_int, [_V, _V, _V, _I64, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                               ctypes.c_int, _V, _V, ctypes.c_int, _V, _V, ctypes.c_uint64, _V, _I64,
+                                               _V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_size_t, _V]),
+    "nerf_train_hier_backward": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                _V, _I64, ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t,
+                                                _V]),
+    "nerf_sample_importance_src": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, ctypes.c_int, _V, _V, ctypes.c_uint64,
+                                                  _V, _V, _V, _V]),
+    "nerf_composite_merged_backward": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int, _V, _V, _V, _V, _V]),
     # depth-aware post effects (include/nerfmi.h)
     "nerf_effect_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "nerf_depth_normalize": (ctypes.c_int, [_V, _I64, _V, _V, ctypes.c_size_t, _V]),

@@ -36,9 +36,9 @@ struct TrainWs {
   float *sigma_live, *rgb_live, *dsigma_live, *drgb_live;
 };
 
-static size_t train_carve(int64_t B, int N, bool occ, void* base, TrainWs& w) {
+// one sample set's regions, dirs .. grad (the hierarchical step carves two of them)
+static void carve_part(Carver& c, int64_t B, int N, TrainWs& w) {
   const size_t b = (size_t)B, M = b * (size_t)N, MT = (size_t)tile_rows((int64_t)M);   // tile-major rows (layout.h)
-  Carver c{(char*)base};
   w.dirs = c.take<float>(b * 3 * 4);
   w.z = c.take<float>(b * N * 4);
   w.feat = c.take<float>(b * kRayFeat * 4);
@@ -52,12 +52,20 @@ static size_t train_carve(int64_t B, int N, bool occ, void* base, TrainWs& w) {
   w.save = c.take<float>(MT * kSaveRow * 4);
   w.masks = c.take<uint32_t>(M * kMaskRow * 4);
   w.grad = c.take<float>(MT * kGradRow * 4);
-  const size_t wg = c.at;
-  w.wgrad = c.take<float>(max_wgrad_floats((int64_t)M) * 4);
-  w.wgrad_floats = (c.at - wg) / 4;
+  w.wgrad = nullptr;
+  w.wgrad_floats = 0;
   w.live = nullptr;
   w.blocks = nullptr;
   w.sigma_live = w.rgb_live = w.dsigma_live = w.drgb_live = nullptr;
+}
+
+static size_t train_carve(int64_t B, int N, bool occ, void* base, TrainWs& w) {
+  const size_t M = (size_t)B * (size_t)N;
+  Carver c{(char*)base};
+  carve_part(c, B, N, w);
+  const size_t wg = c.at;
+  w.wgrad = c.take<float>(max_wgrad_floats((int64_t)M) * 4);
+  w.wgrad_floats = (c.at - wg) / 4;
   if (occ) {
     w.live = c.take<int>(M * 4);
     w.blocks = c.take<uint32_t>(occ_block_count_bytes((int64_t)M));
@@ -77,13 +85,81 @@ static int train_ws(const char* fn, int64_t B, int N, bool occ, void* workspace,
   return NERF_OK;
 }
 
+// floats of state_dict tensor p (nerf_pack_weights order)
+static size_t param_floats(int p) {
+  if (p < 16) {
+    const int L = p / 2;
+    if (p % 2) return kHidden;
+    return (size_t)kHidden * (L == 0 ? kPosEnc : L == kSkipLayer ? kHidden + kPosEnc : kHidden);
+  }
+  switch (p) {
+    case P_SIGMA_W: return kHidden;
+    case P_SIGMA_B: return 1;
+    case P_DIR_W: return (size_t)kDirHidden * (kHidden + kDirEnc);
+    case P_DIR_B: return kDirHidden;
+    case P_APP_W: return (size_t)kDirHidden * kAppDim;
+    case P_APP_B: return kDirHidden;
+    case P_RGB_W: return 3 * kDirHidden;
+    default: return 3;
+  }
+}
+// ... and of a second gradient set with every tensor at a 64-float boundary
+static size_t grad_set_floats() {
+  size_t n = 0;
+  for (int p = 0; p < P_COUNT; ++p) n += (param_floats(p) + 63) & ~(size_t)63;
+  return n;
+}
+
+// The hierarchical step's workspace: the coarse sample set's regions as above (dirs, feat
+// and encd serve both passes), then the fine set's ((B, Nf): z = z_fine, its own rgb .. grad rows; its
+// per-ray regions are unused), then
+//   w_c (B,N) | z_all (B,N+Nf) | merged_src (B,N+Nf) uint16 | the fine part's parameter gradients
+//   (every tensor at a 64-float boundary) | its dapp (B,32) | wgrad partials, sized for the larger part
+struct HierWs {
+  TrainWs c, f;
+  float *w_c, *z_all;
+  uint16_t* src;
+  float *grad2, *dapp2, *wgrad;
+  size_t wgrad_floats;
+};
+
+static bool hier_shape_ok(int64_t B, int N, int Nf) {
+  return B >= 0 && N >= 2 && N <= 256 && Nf >= 1 && Nf <= 1024 && B * (int64_t)N < ((int64_t)1 << 31) &&
+         B * (int64_t)Nf < ((int64_t)1 << 31);
+}
+
+static size_t hier_carve(int64_t B, int N, int Nf, void* base, HierWs& h) {
+  const size_t b = (size_t)B, T = (size_t)(N + Nf);
+  Carver c{(char*)base};
+  carve_part(c, B, N, h.c);
+  carve_part(c, B, Nf, h.f);
+  h.w_c = c.take<float>(b * N * 4);
+  h.z_all = c.take<float>(b * T * 4);
+  h.src = c.take<uint16_t>((b * T + 1) / 2 * 4);
+  h.grad2 = c.take<float>(grad_set_floats() * 4);
+  h.dapp2 = c.take<float>(b * kAppDim * 4);
+  const size_t wc = max_wgrad_floats((int64_t)b * N), wf = max_wgrad_floats((int64_t)b * Nf), wg = c.at;
+  h.wgrad = c.take<float>((wc > wf ? wc : wf) * 4);
+  h.wgrad_floats = (c.at - wg) / 4;
+  return c.at;
+}
+
+static int hier_ws(const char* fn, int64_t B, int N, int Nf, void* workspace, size_t ws_bytes, HierWs& h) {
+  const size_t need = hier_carve(B, N, Nf, workspace, h);
+  if (B > 0 && ws_bytes < need)
+    return set_error(NERF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+  return NERF_OK;
+}
+
 // What the last forward on a workspace was (a small host-side table keyed by workspace address): the
-// MLP arithmetic it ran under, whether it was nerf_train_occ_forward, and then its M_live.  The dense
-// backward picks the mask source from the arithmetic (the f32 forward writes no mask rows), not from
-// the setting in force at backward time; each backward refuses a workspace the other forward wrote.
+// MLP arithmetic it ran under, which step it belonged to (dense, occupancy grid, hierarchical), and for
+// nerf_train_occ_forward its M_live.  A backward picks the mask source from the arithmetic (the f32
+// forward writes no mask rows), not from the setting in force at backward time; each backward refuses
+// a workspace another step's forward wrote.
+enum StepKind { kStepDense, kStepOcc, kStepHier };
 struct ForwardRecord {
   int arith;
-  bool occ;
+  StepKind kind;
   int64_t M_live;
 };
 static std::mutex g_ws_mu;
@@ -504,7 +580,7 @@ int nerf_train_forward(const float* packed, const float* rays_o, const float* ra
   if ((rc = launch_mlp(packed, rays_o, w.dirs, w.z, B, N, w.feat, w.rgb, w.sigma, nullptr, 0, s, w.save, w.encd,
                        w.masks)))
     return rc;                                                                                          // :49
-  remember_forward(workspace, {g_mlp_arith, false, 0});
+  remember_forward(workspace, {g_mlp_arith, kStepDense, 0});
   return forward_tail("nerf_train_forward", w, B, N, rgb_map, depth_map, weights_out, z_out, s);
 }
 
@@ -525,7 +601,7 @@ int nerf_train_backward(const float* packed, const float* packedT, const float* 
   // follow the arithmetic in force now (an f16x3 backward after an f32 forward reads the ReLU masks
   // from the saved activations instead)
   ForwardRecord fwd;
-  if (!last_forward(workspace, fwd) || fwd.occ)
+  if (!last_forward(workspace, fwd) || fwd.kind != kStepDense)
     return set_error(NERF_ERR_BAD_ARG, "nerf_train_backward: no nerf_train_forward wrote this workspace");
   const uint32_t* masks = fwd.arith == NERF_ARITH_F16X3 ? w.masks : nullptr;
   const int64_t M = B * N;
@@ -534,25 +610,6 @@ int nerf_train_backward(const float* packed, const float* packedT, const float* 
                                 /*store_dhd=*/!fused_ray_sums(N))))
     return rc;
   return param_grads(w.save, w.grad, M, N, app, app_rows, packed, param_grads_out, dapp, w.wgrad, w.wgrad_floats, s);
-}
-
-// floats of state_dict tensor p (nerf_pack_weights order)
-static size_t param_floats(int p) {
-  if (p < 16) {
-    const int L = p / 2;
-    if (p % 2) return kHidden;
-    return (size_t)kHidden * (L == 0 ? kPosEnc : L == kSkipLayer ? kHidden + kPosEnc : kHidden);
-  }
-  switch (p) {
-    case P_SIGMA_W: return kHidden;
-    case P_SIGMA_B: return 1;
-    case P_DIR_W: return (size_t)kDirHidden * (kHidden + kDirEnc);
-    case P_DIR_B: return kDirHidden;
-    case P_APP_W: return (size_t)kDirHidden * kAppDim;
-    case P_APP_B: return kDirHidden;
-    case P_RGB_W: return 3 * kDirHidden;
-    default: return 3;
-  }
 }
 
 int nerf_train_occ_sample(const float* rays_o, const float* rays_d, int64_t B, double near, double far, int N,
@@ -591,7 +648,7 @@ int nerf_train_occ_forward(const float* packed, const float* rays_o, int64_t B, 
   if ((rc = launch_mlp16_live(packed, rays_o, w.dirs, w.z, N, w.feat, w.encd, w.live, M_live, w.rgb, w.sigma, w.rgb_live,
                               w.sigma_live, w.save, w.masks, s)))
     return rc;
-  remember_forward(workspace, {g_mlp_arith, true, M_live});
+  remember_forward(workspace, {g_mlp_arith, kStepOcc, M_live});
   return forward_tail("nerf_train_occ_forward", w, B, N, rgb_map, depth_map, weights_out, z_out, s);
 }
 
@@ -608,7 +665,7 @@ int nerf_train_occ_backward(const float* packed, const float* packedT, const flo
   TrainWs w;
   if ((rc = train_ws("nerf_train_occ_backward", B, N, true, workspace, ws_bytes, w))) return rc;
   ForwardRecord fwd;
-  if (!last_forward(workspace, fwd) || !fwd.occ || fwd.M_live != M_live)
+  if (!last_forward(workspace, fwd) || fwd.kind != kStepOcc || fwd.M_live != M_live)
     return set_error(NERF_ERR_BAD_ARG, "nerf_train_occ_backward: no nerf_train_occ_forward with M_live=%lld wrote this "
                      "workspace", (long long)M_live);
   hipStream_t s = (hipStream_t)stream;
@@ -627,6 +684,163 @@ int nerf_train_occ_backward(const float* packed, const float* packedT, const flo
     return rc;
   return param_grads(w.save, w.grad, M_live, 1, app, app_rows, packed, param_grads_out, dapp, w.wgrad,
                      w.wgrad_floats, s);
+}
+
+// ------------------------------------------------------------- the hierarchical step
+// One network, two sample sets: the coarse pass of nerf_train_forward on (B, N), the H1 resample of its
+// weights (positions are constants of the step), the forward with saves on the Nf new samples, and the
+// merged composite over N + Nf.  The backward sums the coarse composite's term (scaled by coarse_weight)
+// and the merged composite's into the coarse rows, runs the data and weight gradients once per part,
+// each with its own per-ray length, and adds the fine part's gradients to the coarse part's.
+static int check_hier_shape(const char* fn, int64_t B, int N, int Nf) {
+  REQUIRE(B >= 0, "%s: B=%lld", fn, (long long)B);
+  if (N < 2 || N > 256 || Nf < 1 || Nf > 1024)
+    return set_error(NERF_ERR_UNSUPPORTED, "%s: N=%d (2..256) Nf=%d (1..1024)", fn, N, Nf);
+  REQUIRE(hier_shape_ok(B, N, Nf), "%s: B*N=%lld B*Nf=%lld too large", fn, (long long)B * N, (long long)B * Nf);
+  return NERF_OK;
+}
+
+size_t nerf_train_hier_workspace_bytes(int64_t B, int N, int Nf) {
+  if (!hier_shape_ok(B, N, Nf)) return 0;
+  HierWs h;
+  return hier_carve(B, N, Nf, nullptr, h);
+}
+
+int nerf_train_hier_forward(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
+                            double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
+                            const float* t_rand, const float* u_rand, uint64_t seed, const float* app,
+                            int64_t app_rows, float* rgb_map, float* depth_map, float* weights_out, float* z_out,
+                            float* coarse_rgb, float* coarse_depth, float* coarse_weights_out, void* workspace,
+                            size_t ws_bytes, nerf_stream_t stream) {
+  const char* fn = "nerf_train_hier_forward";
+  int rc;
+  if ((rc = check_hier_shape(fn, B, N, Nf))) return rc;
+  REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "%s: app_rows=%lld with B=%lld", fn, (long long)app_rows,
+          (long long)B);
+  if (B == 0) return NERF_OK;
+  REQUIRE(packed && rays_o && rays_d && t_vals && u_lin && rgb_map && depth_map && coarse_rgb && coarse_depth &&
+              workspace && (app_rows == 0 || app),
+          "%s: null pointer", fn);
+  HierWs h;
+  if ((rc = hier_ws(fn, B, N, Nf, workspace, ws_bytes, h))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const TrainWs &c = h.c, &f = h.f;
+  // the coarse pass: nerf_train_forward's sequence
+  if ((rc = launch_ray_features(packed, rays_d, B, app, app_rows, c.feat, s, c.encd, c.dirs))) return rc;
+  if ((rc = launch_stratified(rays_o, c.dirs, B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand, seed, c.z,
+                              nullptr, s)))
+    return rc;
+  if ((rc = launch_mlp(packed, rays_o, c.dirs, c.z, B, N, c.feat, c.rgb, c.sigma, nullptr, 0, s, c.save, c.encd, c.masks)))
+    return rc;
+  remember_forward(workspace, {g_mlp_arith, kStepHier, 0});
+  float* wc = coarse_weights_out ? coarse_weights_out : h.w_c;
+  if ((rc = launch_composite(c.rgb, c.sigma, c.z, B, N, coarse_rgb, coarse_depth, wc, s))) return rc;
+  // the resample (the draws of nerf_render_rays at ray0 = 0), the Nf new samples, the merged composite
+  if ((rc = launch_importance(nullptr, nullptr, c.z, wc, B, N, Nf, u_lin, u_rand, seed ^ 0x5DEECE66Dull, h.z_all, nullptr,
+                              nullptr, nullptr, nullptr, nullptr, f.z, nullptr, s, h.src)))
+    return rc;
+  if ((rc = launch_mlp(packed, rays_o, c.dirs, f.z, B, Nf, c.feat, f.rgb, f.sigma, nullptr, 0, s, f.save, c.encd,
+                       f.masks)))
+    return rc;
+  if ((rc = launch_composite_merged(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, B, N, Nf, rgb_map, depth_map,
+                                    weights_out, s)))
+    return rc;
+  if (z_out && hipMemcpyAsync(z_out, h.z_all, (size_t)B * (N + Nf) * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "%s: z copy failed", fn);
+  return NERF_OK;
+}
+
+int nerf_train_hier_backward(const float* packed, const float* packedT, const float* rgb_map, const float* coarse_rgb,
+                             const float* target, int64_t B, int N, int Nf, double coarse_weight, const float* app,
+                             int64_t app_rows, float* const* param_grads_out, float* dapp, float* loss,
+                             void* workspace, size_t ws_bytes, nerf_stream_t stream) {
+  const char* fn = "nerf_train_hier_backward";
+  int rc;
+  if ((rc = check_hier_shape(fn, B, N, Nf))) return rc;
+  REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "%s: app_rows=%lld", fn, (long long)app_rows);
+  REQUIRE(coarse_weight >= 0.0 && coarse_weight <= 3.0e38, "%s: coarse_weight=%g", fn, coarse_weight);
+  if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
+                                workspace)))
+    return rc;
+  REQUIRE(B == 0 || coarse_rgb, "%s: null pointer", fn);
+  if (B == 0) return NERF_OK;
+  HierWs h;
+  if ((rc = hier_ws(fn, B, N, Nf, workspace, ws_bytes, h))) return rc;
+  ForwardRecord fwd;
+  if (!last_forward(workspace, fwd) || fwd.kind != kStepHier)
+    return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_hier_forward wrote this workspace", fn);
+  hipStream_t s = (hipStream_t)stream;
+  const TrainWs &c = h.c, &f = h.f;
+  const bool f16 = fwd.arith == NERF_ARITH_F16X3;
+  const double mse_scale = 2.0 / (3.0 * (double)B);
+  // the coarse composite's term, then the merged composite's on top of it in the coarse rows
+  if ((rc = launch_composite_backward(c.rgb, c.sigma, c.z, coarse_rgb, target, nullptr, nullptr, B, N,
+                                      (float)(coarse_weight * mse_scale), c.dsigma, c.drgb, c.sq_err, s)))
+    return rc;
+  if ((rc = launch_composite_merged_backward(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, rgb_map, target, nullptr,
+                                             nullptr, B, N, Nf, (float)mse_scale, 1, c.dsigma, c.drgb, f.dsigma, f.drgb,
+                                             f.sq_err, s)))
+    return rc;
+  if ((rc = launch_loss(f.sq_err, B, loss, s))) return rc;
+  if ((rc = launch_loss(c.sq_err, B, loss + 1, s))) return rc;
+  // the fine part's gradients go to the workspace's second set
+  float* g2[P_COUNT];
+  size_t at = 0;
+  for (int p = 0; p < P_COUNT; ++p) {
+    g2[p] = h.grad2 + at;
+    at += (param_floats(p) + 63) & ~(size_t)63;
+  }
+  if ((rc = launch_mlp_backward(packed, packedT, c.save, f16 ? c.masks : nullptr, c.sigma, c.rgb, c.dsigma, c.drgb, B * N,
+                                c.grad, s, /*store_dhd=*/!fused_ray_sums(N))))
+    return rc;
+  if ((rc = param_grads(c.save, c.grad, B * N, N, app, app_rows, packed, param_grads_out, dapp, h.wgrad, h.wgrad_floats,
+                        s)))
+    return rc;
+  if ((rc = launch_mlp_backward(packed, packedT, f.save, f16 ? f.masks : nullptr, f.sigma, f.rgb, f.dsigma, f.drgb,
+                                B * Nf, f.grad, s, /*store_dhd=*/!fused_ray_sums(Nf))))
+    return rc;
+  if ((rc = param_grads(f.save, f.grad, B * Nf, Nf, app, app_rows, packed, g2, dapp ? h.dapp2 : nullptr, h.wgrad,
+                        h.wgrad_floats, s)))
+    return rc;
+  // coarse + fine, one float add per element (the appearance projection is unused without appearance rows)
+  float* dst[P_COUNT + 1];
+  const float* src[P_COUNT + 1];
+  size_t n[P_COUNT + 1];
+  int count = 0;
+  for (int p = 0; p < P_COUNT; ++p) {
+    if (app_rows == 0 && (p == P_APP_W || p == P_APP_B)) continue;
+    dst[count] = param_grads_out[p], src[count] = g2[p], n[count] = param_floats(p);
+    ++count;
+  }
+  if (dapp && app_rows) dst[count] = dapp, src[count] = h.dapp2, n[count] = (size_t)app_rows * kAppDim, ++count;
+  return launch_add_segments(dst, src, n, count, s);
+}
+
+int nerf_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
+                                   const uint16_t* src, const float* z_all, const float* grad_rgb_map,
+                                   const float* grad_depth_map, int64_t B, int N, int Nf, int accumulate_coarse,
+                                   float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f,
+                                   nerf_stream_t stream) {
+  REQUIRE(B >= 0, "nerf_composite_merged_backward: B=%lld", (long long)B);
+  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_merged_backward: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
+  REQUIRE(B == 0 || (rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c && drgb_c && dsigma_f && drgb_f),
+          "nerf_composite_merged_backward: null pointer");
+  return launch_composite_merged_backward(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, nullptr, nullptr, grad_rgb_map,
+                                          grad_depth_map, B, N, Nf, 0.0f, accumulate_coarse, dsigma_c, drgb_c, dsigma_f,
+                                          drgb_f, nullptr, (hipStream_t)stream);
+}
+
+int nerf_sample_importance_src(const float* z_vals, const float* weights, int64_t B, int N, int Nf, const float* u_lin,
+                               const float* u_rand, uint64_t seed, float* z_all, float* z_fine, uint16_t* merged_src,
+                               nerf_stream_t stream) {
+  REQUIRE(B >= 0, "nerf_sample_importance_src: B=%lld", (long long)B);
+  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_sample_importance_src: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
+  REQUIRE(B == 0 || (z_vals && weights && u_lin && z_all && z_fine && merged_src),
+          "nerf_sample_importance_src: null pointer");
+  return launch_importance(nullptr, nullptr, z_vals, weights, B, N, Nf, u_lin, u_rand, seed, z_all, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, z_fine, nullptr, (hipStream_t)stream, merged_src);
 }
 
 int nerf_mlp_forward_train_live(const float* packed, const float* origins, const float* dirs, const float* z_vals,

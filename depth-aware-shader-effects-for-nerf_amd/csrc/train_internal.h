@@ -70,6 +70,16 @@ inline size_t ray_sum_floats(int64_t M) { return ray_sum_a_floats(M) + ray_sum_b
 int launch_composite_backward(const float* rgb, const float* sigma, const float* z, const float* rgb_map,
                               const float* target, const float* grad_map, const float* grad_depth, int64_t B, int N,
                               float scale, float* dsigma, float* drgb, float* sq_err, hipStream_t s);
+// the same over the merged samples of the hierarchical step (sample p of ray r: src[r (N + Nf) + p] of
+// cat[coarse, fine]); coarse rows take in + term when `accumulate` is set
+int launch_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                                     const float* sigma_f, const uint16_t* src, const float* z_all,
+                                     const float* rgb_map, const float* target, const float* grad_map,
+                                     const float* grad_depth, int64_t B, int N, int Nf, float scale, int accumulate,
+                                     float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f, float* sq_err,
+                                     hipStream_t s);
+// dst[k][i] += src[k][i], i < n[k], for count <= 25 segments in one launch
+int launch_add_segments(float* const* dst, const float* const* src, const size_t* n, int count, hipStream_t s);
 // mlp_backward.hip
 int launch_packT(const float* const* params, float* packedT, hipStream_t s);
 void packT_host(const float* const* params, float* packedT);

@@ -82,7 +82,8 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
                 f"nerfmi.volume_render({what}) has no differentiable path: the reference's fine pass is a stub "
                 f"with no training semantics (src/render.py:83-86) and the staged/timed paths are inference "
                 f"instrumentation.  Render under torch.no_grad() (as the reference's run.py:217 does) or with "
-                f"parameters that do not require grad; the coarse call (hierarchical=False) is differentiable.")
+                f"parameters that do not require grad; the coarse call (hierarchical=False) is differentiable, and "
+                f"nerfmi.train.Trainer(hierarchical=True) trains with the fine pass on a coarse + fine loss.")
         return autograd.volume_render_grad(model, rays_o, rays_d, near, far, n_samples, appearance_embedding,
                                            perturb, t_rand=t_rand, seed=seed, ray_offset=ray_offset)
     dev = _lib.device()

@@ -19,6 +19,10 @@ trained values.  The reference's quirks are kept: the fir
 use min(64, batch_size) rays (train.py:26,56-57), StepLR steps only when i % step_size == 0
 (train.py:95-96), n_importance is ignored by the coarse-only volume_render (render.py:83-86),
 and one image's rays form each batch (dataset.py:249-277).
+
+Not a reference feature: ``Trainer(hierarchical=True)`` / ``train_nerf(hierarchical=True)`` run the H1
+fine pass in every step and train on mse(fine) + coarse_loss_weight * mse(coarse)
+(nerf_train_hier_forward / nerf_train_hier_backward).
 """
 import ctypes
 import math
@@ -53,12 +57,21 @@ class Trainer:
     step k >= warmup with k == warmup or k % every == 0 the bits are replaced by
     OccupancyGrid.from_model(self.model, box, resolution, threshold, supersample, dilate).  The
     rebuild is deterministic, so data-parallel ranks (identical weights) rebuild identical bits and
-    nothing is communicated."""
+    nothing is communicated.
+
+    ``hierarchical``: every step also runs the H1 fine pass (``n_importance`` resampled positions per
+    ray, default config.num_importance; one network for both passes, as in the hierarchical render)
+    and trains on loss = mse(fine) + ``coarse_loss_weight`` * mse(coarse) (include/nerfmi_train.h
+    "training with the hierarchical fine pass").  forward_backward then returns that
+    loss with the fine (merged) rgb_map and leaves the two device floats (fine, coarse) on
+    ``self.loss_parts``.  Not combined with ``occupancy``."""
 
     def __init__(self, config, model=None, appearance_embeddings=None, n_images=None, group=None,
                  lr=None, betas=(0.9, 0.999), eps=1e-8, near=None, far=None, occupancy=None,
-                 occupancy_refresh=None):
+                 occupancy_refresh=None, hierarchical=False, n_importance=None, coarse_loss_weight=1.0):
         _check_occupancy_args(occupancy, occupancy_refresh)
+        self.hierarchical, self.n_importance, self.coarse_loss_weight = _check_hierarchical_args(
+            config, hierarchical, n_importance, coarse_loss_weight, occupancy)
         self.config = config
         # the sampling interval: the dataset's near/far (train.py:79 passes dataset.near/far), the
         # config's when no dataset is given
@@ -130,6 +143,9 @@ class Trainer:
         self._ws = None
         self._tvals = {}
         self._side = None          # side stream for the transposed packing (forward_backward)
+        if self.hierarchical:
+            self.loss_parts = torch.zeros(2, device=self.dev)   # (fine, coarse) mean squared errors
+            self._ws_hier = None
         self.occupancy = occupancy
         self.occupancy_refresh = None
         self.live_fraction = None  # share of the last step's samples the grid marked live
@@ -198,10 +214,12 @@ class Trainer:
             self.view(self.grad, 21).zero_()
 
     # ------------------------------------------------------------------------------ one step
-    def forward_backward(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, seed=None, _marks=None):
+    def forward_backward(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, u_rand=None, seed=None,
+                         _marks=None):
         """Loss (device scalar) and gradients in self.grad for one batch (train.py:77-90).
         rays (B,3) and target (B,3) on the device; app_idx: the batch's image (appearance row).
-        t_rand (B,N) = the torch.rand draw of ray_utils.py:80; else the in-kernel RNG on `seed`."""
+        t_rand (B,N) = the torch.rand draw of ray_utils.py:80; else the in-kernel RNG on `seed`.
+        u_rand (B,n_importance): the fine pass's draws (hierarchical trainers only)."""
         lib, s, P = self.lib, _lib.stream(), _lib.ptr
         N = self.config.num_samples
         o, d, tgt = self._batch(rays_o, rays_d, target)
@@ -211,6 +229,10 @@ class Trainer:
             assert t_rand.shape == (B, N)
         if seed is None:
             seed = step_seed(self.steps + 1, self.rank)
+        if self.hierarchical:
+            return self._forward_backward_hier(o, d, tgt, app_idx, t_rand, u_rand, seed, _marks)
+        if u_rand is not None:
+            raise ValueError("Trainer: u_rand belongs to the fine pass; construct the trainer with hierarchical=True")
         if self.occupancy is not None:
             return self._forward_backward_occ(o, d, tgt, app_idx, t_rand, seed, _marks)
         _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
@@ -234,6 +256,45 @@ class Trainer:
                    "nerf_train_backward")
         self._zero_unused_projection(rows)
         return self.loss_buf[0], rgb_map
+
+    def _forward_backward_hier(self, o, d, tgt, app_idx, t_rand, u_rand, seed, _marks=None):
+        """forward_backward with the fine pass: nerf_train_hier_forward + nerf_train_hier_backward on one
+        workspace that carries both sample sets' saves."""
+        lib, s, P = self.lib, _lib.stream(), _lib.ptr
+        N, Nf = self.config.num_samples, self.n_importance
+        B = o.shape[0]
+        if u_rand is not None:
+            u_rand = u_rand.to(self.dev, torch.float32).contiguous()
+            assert u_rand.shape == (B, Nf)
+        _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
+        main = torch.cuda.current_stream(self.dev)
+        self._pack_transposed_aside(main)
+        t_vals = self._t_vals(N)
+        u_lin = linspace_table(Nf, self.dev, drop_last=True)        # ray_utils.py:115
+        need = lib.nerf_train_hier_workspace_bytes(B, N, Nf)
+        if B and need == 0:
+            raise ValueError(f"Trainer: the hierarchical step takes num_samples in 2..256 and n_importance in "
+                             f"1..1024, got {N} + {Nf}")
+        if self._ws_hier is None or self._ws_hier.numel() < need:
+            self._ws_hier = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        ws = self._ws_hier
+        rgb_map, depth = self._maps(B)
+        rgb_c, depth_c = self._maps(B)
+        app, rows = self._app_row(app_idx)
+        _lib.check(lib.nerf_train_hier_forward(P(self.packed), P(o), P(d), B, self.near, self.far, N, Nf, P(t_vals),
+                                               P(u_lin), 1, P(t_rand), P(u_rand), int(seed), P(app), rows,
+                                               P(rgb_map), P(depth), None, None, P(rgb_c), P(depth_c), None, P(ws),
+                                               ws.numel(), s), "nerf_train_hier_forward")
+        if _marks is not None:
+            _marks[1].record(main)
+        dapp = self.app_grad[int(app_idx)] if rows else None
+        main.wait_event(self._join)
+        _lib.check(lib.nerf_train_hier_backward(P(self.packed), P(self.packedT), P(rgb_map), P(rgb_c), P(tgt), B, N, Nf,
+                                                self.coarse_loss_weight, P(app), rows, self.grad_ptrs, P(dapp),
+                                                P(self.loss_parts), P(ws), ws.numel(), s), "nerf_train_hier_backward")
+        self._zero_unused_projection(rows)
+        loss = self.loss_parts[0] + self.coarse_loss_weight * self.loss_parts[1]
+        return loss, rgb_map
 
     def _forward_backward_occ(self, o, d, tgt, app_idx, t_rand, seed, _marks=None):
         """forward_backward on the live samples of self.occupancy: sample + classify, the live count
@@ -358,8 +419,8 @@ class Trainer:
         if r is not None and self.steps >= r["warmup"] and (self.steps == r["warmup"] or self.steps % r["every"] == 0):
             self._rebuild_occupancy()
 
-    def step(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, seed=None):
-        loss, rgb = self.forward_backward(rays_o, rays_d, target, app_idx, t_rand=t_rand, seed=seed)
+    def step(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, u_rand=None, seed=None):
+        loss, rgb = self.forward_backward(rays_o, rays_d, target, app_idx, t_rand=t_rand, u_rand=u_rand, seed=seed)
         self.all_reduce()
         self.optimizer_step()
         return loss
@@ -430,6 +491,29 @@ def _check_occupancy_args(occupancy, occupancy_refresh):
                          f"supersample >= 1")
 
 
+def _check_hierarchical_args(config, hierarchical, n_importance, coarse_loss_weight, occupancy):
+    """(hierarchical, n_importance, coarse_loss_weight) checked; ValueError otherwise (no device needed)."""
+    hierarchical = bool(hierarchical)
+    if not hierarchical:
+        if n_importance is not None:
+            raise ValueError("Trainer: n_importance needs hierarchical=True")
+        if float(coarse_loss_weight) != 1.0:
+            raise ValueError("Trainer: coarse_loss_weight needs hierarchical=True")
+        return False, None, 1.0
+    if occupancy is not None:
+        raise ValueError("Trainer: hierarchical=True is not combined with occupancy= (the hierarchical step "
+                         "runs on every sample)")
+    nf = config.num_importance if n_importance is None else n_importance
+    if isinstance(nf, bool) or not isinstance(nf, (int, np.integer)) or not 1 <= int(nf) <= 1024:
+        raise ValueError(f"Trainer: n_importance must be an integer in 1..1024, got {nf!r}")
+    if not 2 <= int(config.num_samples) <= 256:
+        raise ValueError(f"Trainer: hierarchical=True takes config.num_samples in 2..256, got {config.num_samples}")
+    cw = float(coarse_loss_weight)
+    if not (cw >= 0.0 and math.isfinite(cw)):
+        raise ValueError(f"Trainer: coarse_loss_weight must be finite and >= 0, got {coarse_loss_weight!r}")
+    return True, int(nf), cw
+
+
 def step_seed(key, rank):
     """Key of a step's in-kernel jitter stream: distinct per step and per data-parallel rank (the
     reference draws torch.rand per call, ray_utils.py:80; ranks must not share draws)."""
@@ -462,7 +546,7 @@ def average_gradients(flat_grad, group):
 
 def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iterations=None, log_every=10,
                checkpoint_every=1000, seed=None, plots=True, return_metrics=False, occupancy=None,
-               occupancy_refresh=None):
+               occupancy_refresh=None, hierarchical=False, n_importance=None, coarse_loss_weight=1.0):
     """src/train.py:13-207 on nerfmi: returns the trained model, as the reference does
     (train.py:207; run.py:347 assigns it).  ``return_metrics=True`` returns (model, losses, psnrs)
     instead; the per-iteration losses and PSNRs are also left on ``train_nerf.losses`` /
@@ -472,16 +556,20 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
     Under data parallelism every rank draws its own batch (its own image, its own jitter
     stream) and the gradients are averaged; rank 0 writes.  ``occupancy`` / ``occupancy_refresh``
     go to the Trainer (training on the live samples of an occupancy grid); the final and periodic
-    checkpoints then carry the grid's state_dict under "occupancy"."""
+    checkpoints then carry the grid's state_dict under "occupancy".  ``hierarchical`` /
+    ``n_importance`` / ``coarse_loss_weight`` go to the Trainer too (coarse + fine loss): the logged
+    loss and PSNR are then the fine pass's, and the validation render is hierarchical."""
     import torch.distributed as dist
     _check_occupancy_args(occupancy, occupancy_refresh)
+    _check_hierarchical_args(config, hierarchical, n_importance, coarse_loss_weight, occupancy)
     rank = dist.get_rank(group) if group is not None else 0
     if rank == 0:
         os.makedirs(save_dir, exist_ok=True)
     initial_batch_size = min(64, config.batch_size)                    # train.py:26
     trainer = Trainer(config, appearance_embeddings=getattr(dataset, "appearance_embeddings", None),
                       n_images=len(dataset), group=group, near=getattr(dataset, "near", None),
-                      far=getattr(dataset, "far", None), occupancy=occupancy, occupancy_refresh=occupancy_refresh)
+                      far=getattr(dataset, "far", None), occupancy=occupancy, occupancy_refresh=occupancy_refresh,
+                      hierarchical=hierarchical, n_importance=n_importance, coarse_loss_weight=coarse_loss_weight)
     iters = config.num_iterations if num_iterations is None else num_iterations
     losses, psnrs = [], []
     train_nerf.losses, train_nerf.psnrs = losses, psnrs
@@ -494,7 +582,7 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
                             seed=None if seed is None else step_seed(seed * 1_000_003 + i, trainer.rank))
         if i % config.scheduler_step_size == 0:                          # StepLR, train.py:95-96
             trainer.lr *= config.scheduler_gamma
-        loss_v = float(loss)
+        loss_v = float(trainer.loss_parts[0]) if trainer.hierarchical else float(loss)   # the fine MSE
         psnr_v = -10.0 * math.log10(loss_v) if loss_v > 0 else float("inf")
         losses.append(loss_v)
         psnrs.append(psnr_v)
@@ -503,7 +591,8 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
         if rank == 0 and checkpoint_every and i % checkpoint_every == 0:
             torch.save(trainer.checkpoint(loss_v, psnr_v, i), os.path.join(save_dir, f"checkpoint_{i:06d}.pt"))
             if plots:
-                validation_render(trainer.model, dataset, config, i, save_dir)
+                validation_render(trainer.model, dataset, config, i, save_dir, hierarchical=trainer.hierarchical,
+                                  n_importance=trainer.n_importance)
     if rank == 0:
         torch.save(trainer.checkpoint(loss_v, psnr_v, iters), os.path.join(save_dir, "checkpoint_final.pt"))
         if plots:
@@ -515,9 +604,10 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
 
 
 @torch.no_grad()
-def validation_render(model, dataset, config, iteration, save_dir):
+def validation_render(model, dataset, config, iteration, save_dir, hierarchical=False, n_importance=None):
     """The sample render of train.py:127-173: the first 1000 rays of the last image, coarse
-    volume_render with perturb=False, RGB and viridis depth side by side in
+    volume_render with perturb=False (``hierarchical``: the H1 fine pass with n_importance samples, as
+    a hierarchical trainer trained it), RGB and viridis depth side by side in
     render_{iteration:06d}.png.  Returns (rgb (1000,3), depth (1000,1))."""
     from .render import volume_render
     val = dataset.get_rays(idx=len(dataset) - 1)
@@ -526,7 +616,8 @@ def validation_render(model, dataset, config, iteration, save_dir):
     if config.use_appearance:
         app = dataset.appearance_embeddings[val["appearance_idx"]]
     rgb, depth, _ = volume_render(model, o, d, near=dataset.near, far=dataset.far, n_samples=config.num_samples,
-                                  n_importance=config.num_importance, appearance_embedding=app, perturb=False)
+                                  n_importance=config.num_importance if n_importance is None else n_importance,
+                                  appearance_embedding=app, perturb=False, hierarchical=hierarchical)
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt

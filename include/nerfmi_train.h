@@ -101,7 +101,60 @@ int nerf_train_occ_backward(const float* packed, const float* packedT, const flo
                             float* const* param_grads, float* dapp, float* loss, void* workspace, size_t ws_bytes,
                             nerf_stream_t stream);
 
+/* ------------------------------------------------ training with the hierarchical fine pass
+ * One step on B rays with a coarse + fine loss, one network for both passes as in the H1 render
+ * (nerfmi.h, nerf_render_rays with Nf > 0).
+ *
+ * Forward: the coarse pass exactly as nerf_train_forward on (B, N) (same draws for the same seed) into
+ * coarse_rgb (B,3), coarse_depth (B) and the nullable coarse_weights_out (B,N); the H1 resample of the
+ * coarse weights (draws as nerf_render_rays at ray0 = 0, or u_rand (B,Nf); u_lin as there); the forward
+ * with saves on the Nf new samples only; the merged composite over N + Nf into rgb_map, depth_map and
+ * the nullable weights_out / z_out (B,N+Nf).  The resampled positions are constants of the step: no
+ * gradient reaches the coarse weights through them.
+ *
+ * Backward: loss = mse(rgb_map, target) + coarse_weight * mse(coarse_rgb, target), coarse_weight >= 0.
+ * loss[0] (device float) receives the fine mean squared error, loss[1] the coarse one.  A coarse
+ * sample's (dsigma, drgb) is the sum of its coarse-composite and merged-composite terms (so coarse rows
+ * carry a gradient at coarse_weight = 0 too), a fine sample's its merged term.  The data and weight
+ * gradients run once per part ((B*N, N) and (B*Nf, Nf)) and the two parts are added, one float add per
+ * element in a fixed order: param_grads and dapp are written, not accumulated, and deterministic.
+ *
+ * N in 2..256 and Nf in 1..1024 (else NERF_ERR_UNSUPPORTED); B*N and B*Nf < 2^31; app_rows 0, 1 or B;
+ * both arithmetics.  Not combined with an occupancy grid.  The workspace (0 bytes for refused shapes)
+ * holds both parts' saves; a backward refuses (NERF_ERR_BAD_ARG) a workspace whose last forward was
+ * not the hierarchical one, and the dense and occupancy backwards refuse one it wrote. */
+size_t nerf_train_hier_workspace_bytes(int64_t B, int N, int Nf);
+int nerf_train_hier_forward(const float* packed, const float* rays_o, const float* rays_d, int64_t B,
+                            double near, double far, int N, int Nf, const float* t_vals,
+                            const float* u_lin, int perturb, const float* t_rand, const float* u_rand,
+                            uint64_t seed, const float* app, int64_t app_rows, float* rgb_map,
+                            float* depth_map, float* weights_out, float* z_out, float* coarse_rgb,
+                            float* coarse_depth, float* coarse_weights_out, void* workspace,
+                            size_t ws_bytes, nerf_stream_t stream);
+int nerf_train_hier_backward(const float* packed, const float* packedT, const float* rgb_map,
+                             const float* coarse_rgb, const float* target, int64_t B, int N, int Nf,
+                             double coarse_weight, const float* app, int64_t app_rows,
+                             float* const* param_grads, float* dapp, float* loss /* 2 floats */,
+                             void* workspace, size_t ws_bytes, nerf_stream_t stream);
+
 /* -------------------------------------------------------------------- stages */
+/* nerf_sample_importance that emits, beside z_all (B,N+Nf), the fine samples alone in sample order
+ * (z_fine (B,Nf)) and for each merged slot which sample sits there: merged_src (B,N+Nf) uint16, an
+ * index into cat[coarse (N), fine (Nf)].  The form nerf_render_rays uses internally. */
+int nerf_sample_importance_src(const float* z_vals, const float* weights, int64_t B, int N, int Nf,
+                               const float* u_lin, const float* u_rand, uint64_t seed, float* z_all,
+                               float* z_fine, uint16_t* merged_src, nerf_stream_t stream);
+/* nerf_composite_backward_grad over the N + Nf merged samples of a ray: merged sample p of ray r is
+ * sample e = merged_src[r*(N+Nf) + p] of cat[coarse, fine], row r*N + e of (rgb_c, sigma_c) when e < N,
+ * else row r*Nf + e - N of (rgb_f, sigma_f); z from z_all.  Results go to the same split rows (one
+ * writer per element); coarse rows take in + term when accumulate_coarse is set, fine rows are always
+ * written.  The same arithmetic in the same order as the dense kernel on the gathered rows: the same
+ * bits.  N in 1..256, Nf in 1..1024. */
+int nerf_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                                   const float* sigma_f, const uint16_t* merged_src, const float* z_all,
+                                   const float* grad_rgb_map, const float* grad_depth_map, int64_t B,
+                                   int N, int Nf, int accumulate_coarse, float* dsigma_c, float* drgb_c,
+                                   float* dsigma_f, float* drgb_f, nerf_stream_t stream);
 /* nerf_mlp_forward_train (f16x3 only) on the M_live samples the ascending list `live` names (sample
  * r*N + s of the (R, N) launch): COMPACT row i is sample live[i].  save (NERF_TILE_ROWS(M_live) rows),
  * masks (M_live rows), rgb_live (M_live,3) and sigma_live (M_live) are what nerf_mlp_forward_train at

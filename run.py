@@ -16,7 +16,8 @@ in ray chunks (0 = whole frame per call); --occupancy RES builds an occupancy gr
 its set cells in every frame (nerfmi.OccupancyGrid; not a reference feature); in --mode train the
 same two flags train on the live samples of a RES^3 grid over that box, which the trainer keeps
 current from its own model (all ones for the first 256 steps, then rebuilt every 256 steps), and the
-checkpoints carry the grid.  Under torchrun every frame is ray-sharded across
+checkpoints carry the grid; --mode train --hierarchical [--n_importance K] trains with the fine pass on
+a coarse + fine loss (the logged PSNR is the fine pass's; not combined with --occupancy).  Under torchrun every frame is ray-sharded across
 the ranks (frames.py) and rank 0 writes the images.
 --mode train runs the reference's training loop (run.py:326-347 -> src/train.py) on the nerfmi
 kernels (nerfmi.train.train_nerf; the nerf_synthetic scene when present, else the
@@ -84,7 +85,11 @@ def parse_args(argv=None):
     p.add_argument('--iterations', type=int, default=None, help='training iterations (default Config)')
     p.add_argument('--save_dir', type=str, default='checkpoints',
                    help="training checkpoint directory (the reference's train_nerf default, train.py:13)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.mode == 'train' and args.hierarchical and args.occupancy:
+        p.error("--hierarchical and --occupancy are not combined in --mode train (the hierarchical step runs on "
+                "every sample)")
+    return args
 
 
 class SceneInfo:
@@ -253,8 +258,14 @@ def main(argv=None):
             occ_kw = dict(occupancy=nerfmi.OccupancyGrid((-x,) * 3, (x,) * 3, args.occupancy), occupancy_refresh={})
             if rank == 0:
                 print(f"Training with an occupancy grid {args.occupancy}^3 over [-{x:g}, {x:g}]^3")
+        hier_kw = {}
+        if args.hierarchical:   # coarse + fine loss (train.py, Trainer(hierarchical=True)); PSNR of the fine pass
+            hier_kw = dict(hierarchical=True, n_importance=args.n_importance)
+            if rank == 0:
+                n_imp = config.num_importance if args.n_importance is None else args.n_importance
+                print(f"Training hierarchically: {config.num_samples} coarse + {n_imp} fine samples per ray")
         model = train_nerf(config, dataset, save_dir=args.save_dir, num_iterations=args.iterations,   # run.py:347
-                           group=group, **occ_kw)
+                           group=group, **occ_kw, **hier_kw)
         if group is not None:
             dist.destroy_process_group()
         return 0
