@@ -102,6 +102,19 @@ _SIGNATURES = {
                                             _I64, _V, ctypes.c_int, ctypes.POINTER(ctypes.c_float),
                                             ctypes.POINTER(ctypes.c_float), _V, _V, _V, _V, _V, _V, _V,
                                             ctypes.c_size_t, _V]),
+    # opacity map and background (include/nerfmi.h): the originals' arguments, then bg, bg_rows, bd,
+    # acc_map (and coarse_acc) in front of the stream
+    "nerf_composite_bg": (ctypes.c_int, [_V, _V, _V, _I64, ctypes.c_int, _V, _V, _V, _V, _I64, ctypes.c_float, _V,
+                                         _V]),
+    "nerf_render_rays_bg": (ctypes.c_int, [_V, _V, _V, _I64, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                           ctypes.c_int, _V, _V, ctypes.c_int, _V, _V, ctypes.c_uint64, _I64, _V,
+                                           _I64, _V, _V, _V, _V, _V, _V, _V, ctypes.c_size_t, _V, _I64,
+                                           ctypes.c_float, _V, _V, _V]),
+    "nerf_render_rays_occ_bg": (ctypes.c_int, [_V, _V, _V, _I64, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                               ctypes.c_int, _V, _V, ctypes.c_int, _V, _V, ctypes.c_uint64, _I64, _V,
+                                               _I64, _V, ctypes.c_int, ctypes.POINTER(ctypes.c_float),
+                                               ctypes.POINTER(ctypes.c_float), _V, _V, _V, _V, _V, _V, _V,
+                                               ctypes.c_size_t, _V, _I64, ctypes.c_float, _V, _V, _V]),
     # training (include/nerfmi_train.h)
     "nerf_packed_transposed_floats": (ctypes.c_size_t, []),
     "nerf_pack_weights_transposed": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
@@ -151,6 +164,22 @@ _SIGNATURES = {
                                                   _V, _V, _V, _V]),
     "nerf_composite_merged_backward": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_int, _V, _V, _V, _V, _V]),
+    # training with a background (include/nerfmi_train.h): the originals' arguments, then alpha, bg, bg_rows,
+    # acc_weight, rgb_final (and coarse_final) / g_acc, bd in front of the stream
+    "nerf_train_backward_bg": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _I64,
+                                              ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V, _V,
+                                              _I64, ctypes.c_double, _V, _V]),
+    "nerf_train_occ_backward_bg": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _I64, _V, _I64,
+                                                  ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V,
+                                                  _V, _I64, ctypes.c_double, _V, _V]),
+    "nerf_train_hier_backward_bg": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_double, _V, _I64, ctypes.POINTER(ctypes.c_void_p), _V, _V,
+                                                   _V, ctypes.c_size_t, _V, _V, _I64, ctypes.c_double, _V, _V, _V]),
+    "nerf_composite_backward_grad_acc": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V,
+                                                        ctypes.c_float, _V]),
+    "nerf_composite_merged_backward_acc": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_int, _V, _V, _V, _V, _V,
+                                                          ctypes.c_float, _V]),
     # depth-aware post effects (include/nerfmi.h)
     "nerf_effect_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "nerf_depth_normalize": (ctypes.c_int, [_V, _I64, _V, _V, ctypes.c_size_t, _V]),

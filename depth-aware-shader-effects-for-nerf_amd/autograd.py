@@ -22,6 +22,9 @@ plus the table steps exactly as in the reference.  Gradients with respect to ray
 directions or sample positions are not part of the reference's training and are refused loudly.
 ``extras['weights']`` and ``extras['z_vals']`` are returned without a gradient (marked
 non-differentiable: a loss built on them alone raises at backward instead of returning zeros).
+With ``background=``, ``background_depth=`` or ``return_acc=`` (render.py) the forward's
+composite is nerf_composite_bg and the backward nerf_composite_backward_grad_acc: the blended rgb_map,
+the depth with the background at its depth and ``extras['acc_map']`` all carry gradients.
 """
 import ctypes
 
@@ -160,19 +163,28 @@ class _RenderFn(torch.autograd.Function):
                    "nerf_ray_features_train")
         _lib.check(lib.nerf_mlp_forward_train(P(packed), P(o), P(dn), P(z), B, N, P(feat), P(encd), P(rgb), P(sigma),
                                               P(save), P(masks), s), "nerf_mlp_forward_train")      # :49
-        _lib.check(lib.nerf_composite(P(rgb), P(sigma), P(z), B, N, P(rgb_map), P(depth), P(weights), s),
-                   "nerf_composite")                                                                # :56-80
+        bgs = spec.get("bg")      # (bg, bg_rows, bd): the composite with the background and the opacity map
+        acc = torch.empty(B, device=dev) if bgs else None
+        if bgs:
+            _lib.check(lib.nerf_composite_bg(P(rgb), P(sigma), P(z), B, N, P(rgb_map), P(depth), P(weights),
+                                             P(bgs[0]), bgs[1], bgs[2], P(acc), s), "nerf_composite_bg")
+        else:
+            _lib.check(lib.nerf_composite(P(rgb), P(sigma), P(z), B, N, P(rgb_map), P(depth), P(weights), s),
+                       "nerf_composite")                                                            # :56-80
         ctx.spec = dict(B=B, N=N, packed=packed, packedT=packedT, app=appd, rows=rows, keys=spec["keys"],
-                        app_requires_grad=app is not None and app.requires_grad)
+                        app_requires_grad=app is not None and app.requires_grad, bg=bgs)
         ctx.bufs = (z, rgb, sigma, save, masks)
+        ctx.acc = acc
         ctx.params = params
         ctx.app_in = app
         ctx.mark_non_differentiable(weights, z)
         ctx.set_materialize_grads(False)
+        if bgs:
+            return rgb_map, depth, weights, z, acc
         return rgb_map, depth, weights, z
 
     @staticmethod
-    def backward(ctx, g_rgb, g_depth, _gw, _gz):
+    def backward(ctx, g_rgb, g_depth, _gw, _gz, g_acc=None):
         lib, s, P = _lib.load(), _lib.stream(), _lib.ptr
         sp = ctx.spec
         z, rgb, sigma, save, masks = ctx.bufs
@@ -185,13 +197,26 @@ class _RenderFn(torch.autograd.Function):
         g_rgb = None if g_rgb is None else g_rgb.reshape(B, 3).to(dev, torch.float32).contiguous()
         g_depth = None if g_depth is None else g_depth.reshape(B).to(dev, torch.float32).contiguous()
         dsigma, drgb = torch.empty(M, device=dev), torch.empty(M, 3, device=dev)
-        _lib.check(lib.nerf_composite_backward_grad(P(rgb), P(sigma), P(z), P(g_rgb), P(g_depth), B, N, P(dsigma),
-                                                    P(drgb), s), "nerf_composite_backward_grad")
+        if sp["bg"]:
+            # rgb_map = composite + k bg, k = max(0, 1 - acc): d / d acc = -(bg . g_rgb) where k > 0, beside
+            # the caller's own gradient of acc_map (per-ray glue on (B,3); the per-sample work is the kernel's)
+            bg, _, bd = sp["bg"]
+            g_acc = None if g_acc is None else g_acc.reshape(B).to(dev, torch.float32)
+            if bg is not None and g_rgb is not None:
+                through = -((bg * g_rgb).sum(-1)) * (ctx.acc < 1.0)
+                g_acc = through if g_acc is None else g_acc + through
+            g_acc = None if g_acc is None else g_acc.contiguous()
+            _lib.check(lib.nerf_composite_backward_grad_acc(P(rgb), P(sigma), P(z), P(g_rgb), P(g_depth), B, N,
+                                                            P(dsigma), P(drgb), P(g_acc), bd, s),
+                       "nerf_composite_backward_grad_acc")
+        else:
+            _lib.check(lib.nerf_composite_backward_grad(P(rgb), P(sigma), P(z), P(g_rgb), P(g_depth), B, N, P(dsigma),
+                                                        P(drgb), s), "nerf_composite_backward_grad")
         grad = _mlp_backward(sp["packed"], sp["packedT"], save, masks, sigma, rgb, dsigma, drgb, M)
         unused = _COLOUR_KEYS if g_rgb is None else ()
         grads, dapp = _param_grads(sp["keys"], ctx.params, sp["app"], sp["rows"], save, grad, M, N, sp["packed"],
                                    sp["app_requires_grad"] and g_rgb is not None, unused)
-        ctx.bufs = ctx.params = None
+        ctx.bufs = ctx.params = ctx.acc = None
         return (None, _app_grad(dapp, ctx.app_in), *grads)
 
 
@@ -242,7 +267,7 @@ class _MLPFn(torch.autograd.Function):
 
 
 def volume_render_grad(model, rays_o, rays_d, near, far, n_samples, appearance_embedding, perturb, *, t_rand=None,
-                       seed=None, ray_offset=0):
+                       seed=None, ray_offset=0, background=None, background_depth=None, return_acc=False):
     """The differentiable volume_render (render.py:5-97, coarse): (rgb_map, depth_map, extras)."""
     dev = _lib.device()
     orig = rays_o.shape
@@ -265,12 +290,21 @@ def volume_render_grad(model, rays_o, rays_d, near, far, n_samples, appearance_e
     spec = dict(o=o, d=d, B=B, N=N, near=float(near), far=float(far), perturb=bool(perturb), t_rand=tr,
                 seed=int(seed or 0), ray0=int(ray_offset), packed=packed, packedT=packedT, app=appd, rows=rows,
                 keys=keys)
-    rgb_map, depth, weights, z = _RenderFn.apply(spec, app_in, *params)
+    acc = None
+    if background is not None or background_depth is not None or return_acc:
+        from .render import background_rows
+        bg, bg_rows = background_rows(background, B, dev)
+        spec["bg"] = (bg, bg_rows, float("nan") if background_depth is None else float(background_depth))
+        rgb_map, depth, weights, z, acc = _RenderFn.apply(spec, app_in, *params)
+    else:
+        rgb_map, depth, weights, z = _RenderFn.apply(spec, app_in, *params)
     out = rays_o.device
     w = weights.unsqueeze(-1)
     if N == 1:      # the reference's per-sample tensors are empty at one sample (render.py:56-58)
         w = w[:, :0]
     extras = {"weights": w.to(out), "z_vals": z.to(out)}
+    if acc is not None:
+        extras["acc_map"] = acc.reshape(*orig[:-1], 1).to(out)
     return rgb_map.reshape(*orig[:-1], 3).to(out), depth.reshape(*orig[:-1], 1).to(out), extras
 
 

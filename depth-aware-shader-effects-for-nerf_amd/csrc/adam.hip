@@ -56,4 +56,25 @@ int launch_loss(const float* sq_err, int64_t B, float* loss, hipStream_t s) {
   return check_launch("loss_kernel");
 }
 
+// loss = sum(sq_err) / B: the opacity term's mean over the rays, the same reduction
+// (a copy with another divisor, so that loss_kernel, which every existing step launches, stays as it is)
+__global__ void __launch_bounds__(256) loss_rays_kernel(const float* __restrict__ sq_err, int64_t B,
+                                                        float* __restrict__ loss) {
+  __shared__ double part[256];
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < B; i += 256) acc += (double)sq_err[i];
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss = (float)(part[0] / (double)B);
+}
+
+int launch_loss_rays(const float* sq_err, int64_t B, float* loss, hipStream_t s) {
+  hipLaunchKernelGGL(loss_rays_kernel, dim3(1), dim3(256), 0, s, sq_err, B, loss);
+  return check_launch("loss_rays_kernel");
+}
+
 }  // namespace nerf

@@ -473,6 +473,27 @@ int nerf_composite(const float* rgb, const float* sigma, const float* z_vals, in
   return launch_composite(rgb, sigma, z_vals, B, N, rgb_map, depth_map, weights, (hipStream_t)stream);
 }
 
+// The background arguments of the _bg entries: bg_rows in {0, 1, B}, bg non-null when bg_rows > 0.
+static int check_bg(const char* fn, const float* bg, int64_t bg_rows, int64_t B) {
+  REQUIRE(bg_rows == 0 || bg_rows == 1 || bg_rows == B, "%s: bg_rows=%lld with B=%lld (0, 1 or B)", fn,
+          (long long)bg_rows, (long long)B);
+  REQUIRE(bg_rows == 0 || bg, "%s: null bg with bg_rows=%lld", fn, (long long)bg_rows);
+  return NERF_OK;
+}
+
+int nerf_composite_bg(const float* rgb, const float* sigma, const float* z_vals, int64_t B, int N, float* rgb_map,
+                      float* depth_map, float* weights, const float* bg, int64_t bg_rows, float bd, float* acc_map,
+                      nerf_stream_t stream) {
+  REQUIRE(B >= 0, "nerf_composite_bg: B=%lld", (long long)B);
+  if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_bg: N=%d (1..4096)", N);
+  if (int rc = check_bg("nerf_composite_bg", bg, bg_rows, B)) return rc;
+  REQUIRE(B == 0 || (rgb && sigma && z_vals && rgb_map && depth_map), "nerf_composite_bg: null pointer");
+  if (bg_rows == 0 && bd != bd && !acc_map)   // every option off: nerf_composite's launch
+    return launch_composite(rgb, sigma, z_vals, B, N, rgb_map, depth_map, weights, (hipStream_t)stream);
+  const CompositeBg bga{bg_rows ? bg : nullptr, bg_rows > 1 ? 3 : 0, bd, acc_map};
+  return launch_composite_bg(rgb, sigma, z_vals, B, N, rgb_map, depth_map, weights, bga, (hipStream_t)stream);
+}
+
 // --------------------------------------------------------------- occupancy-grid sample skipping
 // (include/nerfmi.h; kernels in occupancy.hip and mlp16s.hip's gathered entry)
 static int check_grid(const char* fn, int G) {
@@ -614,12 +635,19 @@ struct OccGrid {
   int G;
   const float *lo, *inv;
 };
+// The _bg entries' additions (a whole call's, or one ray chunk's); null when every option is off.
+struct RenderBg {
+  const float* bg;
+  int64_t bg_rows;
+  float bd;
+  float *acc_map, *coarse_acc;
+};
 
 // One ray chunk, every argument checked.  With a grid each MLP stage skips the samples outside its
 // set cells: under f16x3 classify -> zero-fill -> the gathered MLP; under NERF_ARITH_F32 every sample
 // is evaluated by the f32 kernel and the classify pass runs after it, zeroing the dead rows (the same
 // result, no speed-up).
-static int render_chunk(const RenderArgs& a, const OccGrid* grid) {
+static int render_chunk(const RenderArgs& a, const OccGrid* grid, const RenderBg* bgo) {
   const int64_t B = a.B;
   const int N = a.N, Nf = a.Nf;
   hipStream_t s = a.s;
@@ -650,6 +678,13 @@ static int render_chunk(const RenderArgs& a, const OccGrid* grid) {
     if ((rc = profiled(s, B * (int64_t)n, dense))) return rc;
     return classify();
   };
+  // the two composites: today's launches, or with a background / opacity request the _bg kernels (the
+  // coarse maps get the same blend)
+  auto composite = [&](float* rgb_map, float* depth, float* wts, float* acc) -> int {
+    if (!bgo) return launch_composite(w.rgb_c, w.sigma_c, z, B, N, rgb_map, depth, wts, s);
+    const CompositeBg bga{bgo->bg_rows ? bgo->bg : nullptr, bgo->bg_rows > 1 ? 3 : 0, bgo->bd, acc};
+    return launch_composite_bg(w.rgb_c, w.sigma_c, z, B, N, rgb_map, depth, wts, bga, s);
+  };
   int rc;
   // render.py:19's normalisation in the ray-feature kernel (it writes dn)
   if ((rc = launch_ray_features(a.packed, a.rays_d, B, a.app, a.app_rows, w.feat, s, nullptr, dn))) return rc;
@@ -657,11 +692,10 @@ static int render_chunk(const RenderArgs& a, const OccGrid* grid) {
                               a.t_rand, seed_c, z, nullptr, s)))
     return rc;                                                                                 // render.py:22
   if ((rc = mlp(z, N, w.rgb_c, w.sigma_c))) return rc;                                         // :49
-  if (Nf == 0)
-    return launch_composite(w.rgb_c, w.sigma_c, z, B, N, a.rgb_map, a.depth_map, wc, s);       // render.py:56-80
+  if (Nf == 0) return composite(a.rgb_map, a.depth_map, wc, bgo ? bgo->acc_map : nullptr);     // render.py:56-80
   float* crgb = a.coarse_rgb ? a.coarse_rgb : w.maps;
   float* cdepth = a.coarse_depth ? a.coarse_depth : w.maps + 3 * B;
-  if ((rc = launch_composite(w.rgb_c, w.sigma_c, z, B, N, crgb, cdepth, wc, s))) return rc;
+  if ((rc = composite(crgb, cdepth, wc, bgo ? bgo->coarse_acc : nullptr))) return rc;
   // H1 fine pass: resample + merge (each merged slot records which coarse or fine sample it holds),
   // the MLP run on the Nf new samples only, in sample order, and the composite over all N+Nf merged
   // samples gathering the coarse evaluations and the fine ones through the map.  (Round 3 scattered
@@ -671,6 +705,11 @@ static int render_chunk(const RenderArgs& a, const OccGrid* grid) {
                               nullptr, nullptr, nullptr, w.z_fine, nullptr, s, w.merged_src)))
     return rc;
   if ((rc = mlp(w.z_fine, Nf, w.rgb_f, w.sigma_f))) return rc;
+  if (bgo) {
+    const CompositeBg bga{bgo->bg_rows ? bgo->bg : nullptr, bgo->bg_rows > 1 ? 3 : 0, bgo->bd, bgo->acc_map};
+    return launch_composite_merged_bg(w.rgb_c, w.sigma_c, w.rgb_f, w.sigma_f, w.merged_src, z_all, B, N, Nf, a.rgb_map,
+                                      a.depth_map, a.weights_out, bga, s);
+  }
   return launch_composite_merged(w.rgb_c, w.sigma_c, w.rgb_f, w.sigma_f, w.merged_src, z_all, B, N, Nf, a.rgb_map,
                                  a.depth_map, a.weights_out, s);
 }
@@ -679,7 +718,8 @@ static int render_chunk(const RenderArgs& a, const OccGrid* grid) {
 // chunks: every per-ray input and output advances by the chunk's first ray, the in-kernel draws stay
 // keyed by the global ray index (ray0 + c0), and each chunk carves the caller's workspace for its own
 // (smaller) B.  The checks that need B > 0 look at the first chunk, the largest.
-static int render_rays(const char* fn, const RenderArgs& a, const OccGrid* grid, size_t ws_bytes) {
+static int render_rays(const char* fn, const RenderArgs& a, const OccGrid* grid, size_t ws_bytes,
+                       const RenderBg* bgo = nullptr) {
   const int64_t B = a.B;
   const int N = a.N, Nf = a.Nf;
   REQUIRE(B >= 0 && a.ray0 >= 0, "%s: B=%lld ray0=%lld", fn, (long long)B, (long long)a.ray0);
@@ -691,6 +731,8 @@ static int render_rays(const char* fn, const RenderArgs& a, const OccGrid* grid,
   }
   REQUIRE(a.app_rows == 0 || a.app_rows == 1 || a.app_rows == B, "%s: app_rows=%lld with B=%lld", fn,
           (long long)a.app_rows, (long long)B);
+  if (bgo)
+    if (int rc = check_bg(fn, bgo->bg, bgo->bg_rows, B)) return rc;
   const int64_t chunk = nerf_render_chunk_rays(N, Nf);
   if (chunk < 1)   // (N + Nf <= 4096 <= the launch limit: unreachable, but never loop on a zero step)
     return set_error(NERF_ERR_UNSUPPORTED, "%s: N=%d Nf=%d exceed the launch limit", fn, N, Nf);
@@ -722,7 +764,17 @@ static int render_rays(const char* fn, const RenderArgs& a, const OccGrid* grid,
     if (c.z_out) c.z_out += c0 * T;
     if (c.coarse_rgb) c.coarse_rgb += 3 * c0;
     if (c.coarse_depth) c.coarse_depth += c0;
-    if (int rc = render_chunk(c, grid)) return rc;
+    RenderBg cb{};
+    if (bgo) {
+      cb = *bgo;
+      if (cb.bg_rows > 1) {      // one colour per ray (a one-ray chunk reads its row at stride 0)
+        cb.bg += 3 * c0;
+        cb.bg_rows = c.B;
+      }
+      if (cb.acc_map) cb.acc_map += c0;
+      if (cb.coarse_acc) cb.coarse_acc += c0;
+    }
+    if (int rc = render_chunk(c, grid, bgo ? &cb : nullptr)) return rc;
   }
   return NERF_OK;
 }
@@ -750,6 +802,38 @@ int nerf_render_rays_occ(const float* packed, const float* rays_o, const float* 
                      (hipStream_t)stream};
   const OccGrid grid{bits, G, lo, inv};
   return render_rays("nerf_render_rays_occ", a, &grid, ws_bytes);
+}
+
+// The same two calls with a background colour / depth and the opacity outputs (include/nerfmi.h).  With
+// every option off (bg_rows 0, bd NaN, no opacity output) they make the calls of the originals.
+int nerf_render_rays_bg(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
+                        double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
+                        const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0, const float* app,
+                        int64_t app_rows, float* rgb_map, float* depth_map, float* weights_out, float* z_out,
+                        float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes, const float* bg,
+                        int64_t bg_rows, float bd, float* acc_map, float* coarse_acc, nerf_stream_t stream) {
+  const RenderArgs a{packed, rays_o, rays_d, B, near, far, N, Nf, t_vals, u_lin, perturb, t_rand, u_rand, seed, ray0,
+                     app, app_rows, rgb_map, depth_map, weights_out, z_out, coarse_rgb, coarse_depth, workspace,
+                     (hipStream_t)stream};
+  const RenderBg bgo{bg, bg_rows, bd, acc_map, coarse_acc};
+  const bool off = bg_rows == 0 && bd != bd && !acc_map && !coarse_acc;
+  return render_rays("nerf_render_rays_bg", a, nullptr, ws_bytes, off ? nullptr : &bgo);
+}
+
+int nerf_render_rays_occ_bg(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
+                            double far, int N, int Nf, const float* t_vals, const float* u_lin, int perturb,
+                            const float* t_rand, const float* u_rand, uint64_t seed, int64_t ray0, const float* app,
+                            int64_t app_rows, const uint32_t* bits, int G, const float* lo, const float* inv,
+                            float* rgb_map, float* depth_map, float* weights_out, float* z_out, float* coarse_rgb,
+                            float* coarse_depth, void* workspace, size_t ws_bytes, const float* bg, int64_t bg_rows,
+                            float bd, float* acc_map, float* coarse_acc, nerf_stream_t stream) {
+  const RenderArgs a{packed, rays_o, rays_d, B, near, far, N, Nf, t_vals, u_lin, perturb, t_rand, u_rand, seed, ray0,
+                     app, app_rows, rgb_map, depth_map, weights_out, z_out, coarse_rgb, coarse_depth, workspace,
+                     (hipStream_t)stream};
+  const OccGrid grid{bits, G, lo, inv};
+  const RenderBg bgo{bg, bg_rows, bd, acc_map, coarse_acc};
+  const bool off = bg_rows == 0 && bd != bd && !acc_map && !coarse_acc;
+  return render_rays("nerf_render_rays_occ_bg", a, &grid, ws_bytes, off ? nullptr : &bgo);
 }
 
 }  // extern "C"

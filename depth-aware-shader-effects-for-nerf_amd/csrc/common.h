@@ -189,5 +189,19 @@ int launch_composite(const float* rgb, const float* sigma, const float* z, int64
 int launch_composite_merged(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
                             const uint16_t* src, const float* z_all, int64_t B, int N, int Nf, float* rgb_map,
                             float* depth, float* weights, hipStream_t s);
+// The composites with the opacity output and the background blend (composite.hip):
+// bg null = no blend, else bg + stride * r is ray r's colour (stride 0: one colour, 3: one per ray);
+// bd NaN = the normalised depth, else the depth of the background; acc_map (B) nullable.
+struct CompositeBg {
+  const float* bg;
+  int stride;
+  float bd;
+  float* acc_map;
+};
+int launch_composite_bg(const float* rgb, const float* sigma, const float* z, int64_t B, int N, float* rgb_map,
+                        float* depth, float* weights, const CompositeBg& bga, hipStream_t s);
+int launch_composite_merged_bg(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
+                               const uint16_t* src, const float* z_all, int64_t B, int N, int Nf, float* rgb_map,
+                               float* depth, float* weights, const CompositeBg& bga, hipStream_t s);
 
 }  // namespace nerf

@@ -72,142 +72,21 @@ struct MergedSrc {
 // composite gathers from there (gathering each sample's 16 bytes from global memory cost 1.14 ms
 // for the 800^2 fine pass against 0.18 ms of staging).
 constexpr int kStageT = 256;
-template <bool VEC, bool MERGED, bool STAGE = false>
-__global__ void __launch_bounds__(256)
-composite_kernel(const float* __restrict__ rgb, const float* __restrict__ sigma, const float* __restrict__ zv,
-                 int64_t B, int N, float* __restrict__ rgb_map, float* __restrict__ depth_map,
-                 float* __restrict__ weights, MergedSrc ms) {
-  extern __shared__ f32x4 quads[];   // STAGE: [8 rays][T]
-  const int k = threadIdx.x & 15;
-  const int rpb = (int)blockDim.x >> 4;                       // rays per block: 16, or 8 when STAGE
-  const int64_t r = (int64_t)blockIdx.x * rpb + (threadIdx.x >> 4);
-  const bool ray = r < B;          // rows past B run on with no samples (the DPP stays inside a row)
-  const int64_t base = ray ? r * N : 0;
-  if constexpr (STAGE) {           // every thread reaches the barrier
-    const int64_t r0 = (int64_t)blockIdx.x * rpb;
-    const int nr = (int)(B - r0 < rpb ? B - r0 : rpb);
-    const int nc = ms.nc, nf = ms.nf;
-    for (int i = threadIdx.x; i < nr * N; i += (int)blockDim.x) {   // quad i: ray i / T, cat index i % T
-      const int rr = i / N, e = i - rr * N;
-      const bool crs = e < nc;
-      const int64_t at = crs ? (r0 + rr) * nc + e : (r0 + rr) * nf + (e - nc);
-      const float* cs = crs ? ms.rgb_c : ms.rgb_f;
-      quads[i] = f32x4{cs[3 * at], cs[3 * at + 1], cs[3 * at + 2], (crs ? ms.sigma_c : ms.sigma_f)[at]};
-    }
-    __syncthreads();
-  }
-  const f32x4* rq = quads + (threadIdx.x >> 4) * N;   // STAGE: this ray's quads
-  if (ray && N == 1 && weights && k == 0) weights[base] = 0.0f;
-  const int n_eff = ray && N > 1 ? N : 0;
-  double carry = 1.0;
-  double acc_r = 0.0, acc_g = 0.0, acc_b = 0.0, acc_wz = 0.0, acc_w = 0.0;
-  for (int c0 = 0; c0 < n_eff; c0 += 64) {
-    const int s0 = c0 + 4 * k;
-    float z[5], sg[4], c[12];
-    if constexpr (MERGED) {
-      int e[4];
-      if (VEC && s0 + 4 <= n_eff) {    // z and the 4 slots' sources as one 16- and one 8-byte load
-        const f32x4 zq = *reinterpret_cast<const f32x4*>(zv + base + s0);
-        const uint2 sq = *reinterpret_cast<const uint2*>(ms.src + base + s0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) z[j] = zq[j];
-        e[0] = (int)(sq.x & 0xffffu), e[1] = (int)(sq.x >> 16), e[2] = (int)(sq.y & 0xffffu), e[3] = (int)(sq.y >> 16);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const bool v = s0 + j < n_eff;
-          z[j] = v ? zv[base + s0 + j] : 0.0f;
-          e[j] = v ? (int)ms.src[base + s0 + j] : -1;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool v = e[j] >= 0;
-        f32x4 q = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (STAGE) {
-          if (v) q = rq[e[j]];
-        } else if (v) {
-          const bool crs = e[j] < ms.nc;
-          const int64_t at = crs ? r * ms.nc + e[j] : r * ms.nf + (e[j] - ms.nc);
-          const float* cs = crs ? ms.rgb_c : ms.rgb_f;
-          q = f32x4{cs[3 * at], cs[3 * at + 1], cs[3 * at + 2], (crs ? ms.sigma_c : ms.sigma_f)[at]};
-        }
-        sg[j] = q[3];
-#pragma unroll
-        for (int c3 = 0; c3 < 3; ++c3) c[3 * j + c3] = q[c3];
-      }
-    } else if (VEC && s0 + 4 <= n_eff) {
-      const f32x4 zq = *reinterpret_cast<const f32x4*>(zv + base + s0);
-      const f32x4 sq = *reinterpret_cast<const f32x4*>(sigma + base + s0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) z[j] = zq[j], sg[j] = sq[j];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const f32x4 cq = *reinterpret_cast<const f32x4*>(rgb + 3 * (base + s0) + 4 * q);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[4 * q + j] = cq[j];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool v = s0 + j < n_eff;
-        z[j] = v ? zv[base + s0 + j] : 0.0f;
-        sg[j] = v ? sigma[base + s0 + j] : 0.0f;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) c[3 * j + q] = v ? rgb[3 * (base + s0 + j) + q] : 0.0f;
-      }
-    }
-    z[4] = s0 + 4 < n_eff ? zv[base + s0 + 4] : 0.0f;
-    float alpha[4];
-    double f[4], lane_prod = 1.0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int s = s0 + j;
-      alpha[j] = 0.0f;
-      f[j] = 1.0;
-      if (s < n_eff) {
-        const float dist = (s + 1 < N) ? z[j + 1] - z[j] : 1e-3f;
-        alpha[j] = 1.0f - expf_rn(-sg[j] * dist);
-        f[j] = (double)((1.0f - alpha[j]) + 1e-10f);
-      }
-      lane_prod *= f[j];
-    }
-    const double incl = row_scan_mul(lane_prod);
-    double pre = carry * row_shr<1>(incl, 1.0);      // product of every factor before this lane's first
-    carry *= __shfl(incl, 15, 16);
-    float w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      w[j] = alpha[j] * (float)pre;                  // 0 past the ray's end (alpha = 0)
-      pre *= f[j];
-      acc_r += (double)(w[j] * c[3 * j]);
-      acc_g += (double)(w[j] * c[3 * j + 1]);
-      acc_b += (double)(w[j] * c[3 * j + 2]);
-      acc_wz += (double)(w[j] * z[j]);
-      acc_w += (double)w[j];
-    }
-    if (weights) {
-      if (VEC && s0 + 4 <= n_eff) {
-        *reinterpret_cast<f32x4*>(weights + base + s0) = f32x4{w[0], w[1], w[2], w[3]};
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (s0 + j < n_eff) weights[base + s0 + j] = w[j];
-      }
-    }
-  }
-  acc_r = row_scan_add(acc_r);
-  acc_g = row_scan_add(acc_g);
-  acc_b = row_scan_add(acc_b);
-  acc_wz = row_scan_add(acc_wz);
-  acc_w = row_scan_add(acc_w);
-  if (ray && k == 15) {
-    rgb_map[3 * r] = (float)acc_r;
-    rgb_map[3 * r + 1] = (float)acc_g;
-    rgb_map[3 * r + 2] = (float)acc_b;
-    depth_map[r] = (float)acc_wz / ((float)acc_w + 1e-10f);
-  }
-}
+
+// composite_bg_kernel: the ray's opacity acc = (float) sum w, the composite's own
+// double sum rounded once, goes to acc_map (nullable), and with k = max(0, 1 - acc)
+//   rgb_map += k * bg[r]            (bg null: no blend; stride 0: one colour, 3: one per ray)
+//   depth    = (float) sum w z + k * bd   (bd NaN: the normalised depth above)
+// each product rounded, then each sum (the library is built without contraction).  An empty ray has
+// acc == 0 and k == 1: colour == bg and depth == bd, bit for bit.  (CompositeBg: common.h.)
+//
+// The kernel, twice (composite_body.h): the plain kernel's text is untouched by the second inclusion.
+#define COMPOSITE_BG 0
+#include "composite_body.h"
+#undef COMPOSITE_BG
+#define COMPOSITE_BG 1
+#include "composite_body.h"
+#undef COMPOSITE_BG
 
 int launch_composite(const float* rgb, const float* sigma, const float* z, int64_t B, int N, float* rgb_map,
                      float* depth, float* weights, hipStream_t s) {
@@ -249,6 +128,49 @@ int launch_composite_merged(const float* rgb_c, const float* sigma_c, const floa
     hipLaunchKernelGGL((composite_kernel<false, true>), grid, dim3(256), 0, s, nullptr, nullptr, z_all, B, T, rgb_map,
                        depth, weights, ms);
   return check_launch("composite_kernel (merged)");
+}
+
+// The same grids, blocks and LDS with composite_bg_kernel (the merged form stages whole rows as above).
+int launch_composite_bg(const float* rgb, const float* sigma, const float* z, int64_t B, int N, float* rgb_map,
+                        float* depth, float* weights, const CompositeBg& bga, hipStream_t s) {
+  if (B == 0) return NERF_OK;
+  const bool vec = N % 4 == 0 && (uintptr_t)rgb % 16 == 0 && (uintptr_t)sigma % 16 == 0 && (uintptr_t)z % 16 == 0 &&
+                   (!weights || (uintptr_t)weights % 16 == 0);
+  const dim3 grid((unsigned)((B + 15) / 16));
+  const MergedSrc none{};
+  if (vec)
+    hipLaunchKernelGGL((composite_bg_kernel<true, false>), grid, dim3(256), 0, s, rgb, sigma, z, B, N, rgb_map, depth,
+                       weights, none, bga);
+  else
+    hipLaunchKernelGGL((composite_bg_kernel<false, false>), grid, dim3(256), 0, s, rgb, sigma, z, B, N, rgb_map, depth,
+                       weights, none, bga);
+  return check_launch("composite_bg_kernel");
+}
+
+int launch_composite_merged_bg(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
+                               const uint16_t* src, const float* z_all, int64_t B, int N, int Nf, float* rgb_map,
+                               float* depth, float* weights, const CompositeBg& bga, hipStream_t s) {
+  if (B == 0) return NERF_OK;
+  const int T = N + Nf;
+  const bool vec = T % 4 == 0 && (uintptr_t)z_all % 16 == 0 && (!weights || (uintptr_t)weights % 16 == 0);
+  const dim3 grid((unsigned)((B + 15) / 16));
+  const MergedSrc ms{rgb_c, sigma_c, rgb_f, sigma_f, src, N, Nf};
+  if (T <= kStageT) {
+    const size_t lds = (size_t)8 * T * sizeof(f32x4);
+    const dim3 grid8((unsigned)((B + 7) / 8));
+    if (vec)
+      hipLaunchKernelGGL((composite_bg_kernel<true, true, true>), grid8, dim3(128), lds, s, nullptr, nullptr, z_all, B,
+                         T, rgb_map, depth, weights, ms, bga);
+    else
+      hipLaunchKernelGGL((composite_bg_kernel<false, true, true>), grid8, dim3(128), lds, s, nullptr, nullptr, z_all, B,
+                         T, rgb_map, depth, weights, ms, bga);
+  } else if (vec)
+    hipLaunchKernelGGL((composite_bg_kernel<true, true>), grid, dim3(256), 0, s, nullptr, nullptr, z_all, B, T, rgb_map,
+                       depth, weights, ms, bga);
+  else
+    hipLaunchKernelGGL((composite_bg_kernel<false, true>), grid, dim3(256), 0, s, nullptr, nullptr, z_all, B, T,
+                       rgb_map, depth, weights, ms, bga);
+  return check_launch("composite_bg_kernel (merged)");
 }
 
 }  // namespace nerf

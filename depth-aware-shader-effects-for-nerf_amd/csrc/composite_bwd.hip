@@ -25,142 +25,6 @@ namespace nerf {
 // surface: dw_s - sum dw_t w_t), and float roundings of dw, w and T there put d sigma twice as far from
 // the float64 gradient as torch's fp32 autograd (tests/test_gpu_degenerate_rays.py).  drgb is the
 // forward's float weight times g.
-__global__ void __launch_bounds__(256)
-composite_backward_kernel(const float* __restrict__ rgb, const float* __restrict__ sigma, const float* __restrict__ zv,
-                          const float* __restrict__ rgb_map, const float* __restrict__ target,
-                          const float* __restrict__ grad_map, const float* __restrict__ grad_depth, int64_t B, int N,
-                          float scale, float* __restrict__ dsigma, float* __restrict__ drgb,
-                          float* __restrict__ sq_err) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= B) return;
-  const int64_t base = r * N;
-  float g[3], se = 0.0f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if (target) {
-      const float e = rgb_map[3 * r + c] - target[3 * r + c];
-      g[c] = scale * e;
-      se += e * e;
-    } else {
-      g[c] = grad_map ? grad_map[3 * r + c] : 0.0f;
-    }
-  }
-  const float gd = grad_depth ? grad_depth[r] : 0.0f;
-  if (lane == 0 && sq_err) sq_err[r] = se;
-  if (N == 1) {                       // the reference's per-sample tensors are empty (render.py:56-58)
-    if (lane == 0) {
-      dsigma[base] = 0.0f;
-      drgb[3 * base] = drgb[3 * base + 1] = drgb[3 * base + 2] = 0.0f;
-    }
-    return;
-  }
-  // pass 1 (forward order): transmittance prefix, carried across 64-sample chunks (and, with a
-  // depth gradient, S and A)
-  // pass 2 (reverse order): suffix sums of dw*w; done chunk by chunk from the end, recomputing
-  // each chunk's T from the stored chunk-start prefixes.
-  const int nchunk = (N + 63) / 64;
-  __shared__ double carry_lds[4][64]; // T at each chunk start (N <= 4096)
-  double* carry_chunk = carry_lds[threadIdx.x >> 6];
-  double carry = 1.0, wz = 0.0, ws = 0.0;
-  for (int c = 0; c < nchunk; ++c) {
-    const int s = c * 64 + lane;
-    double f = 1.0;
-    float alpha = 0.0f, z = 0.0f;
-    if (s < N) {
-      z = zv[base + s];
-      const float dist = (s + 1 < N) ? zv[base + s + 1] - z : 1e-3f;
-      alpha = 1.0f - expf_rn(-sigma[base + s] * dist);
-      f = (double)((1.0f - alpha) + 1e-10f);
-    }
-    double incl = f;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const double up = __shfl_up(incl, off);
-      if (lane >= off) incl *= up;
-    }
-    if (gd != 0.0f) {
-      double excl = __shfl_up(incl, 1);
-      if (lane == 0) excl = 1.0;
-      const double w = (double)alpha * (carry * excl);
-      wz += w * (double)z;
-      ws += w;
-    }
-    if (lane == 0) carry_chunk[c] = carry;
-    carry *= __shfl(incl, 63);
-  }
-  double dinv = 0.0, dmean = 0.0;    // 1 / (A + 1e-10), S / (A + 1e-10)
-  if (gd != 0.0f) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      wz += __shfl_xor(wz, off);
-      ws += __shfl_xor(ws, off);
-    }
-    const double den = ws + (double)1e-10f;
-    dinv = 1.0 / den;
-    dmean = wz * dinv;
-  }
-  __builtin_amdgcn_wave_barrier();
-  double suffix = 0.0;                // sum_{t > current chunk} dw_t w_t
-  for (int c = nchunk - 1; c >= 0; --c) {
-    const int s = c * 64 + lane;
-    const bool valid = s < N;
-    float alpha = 0.0f, dist = 0.0f, e = 1.0f, fs = 1.0f, sg = 0.0f, z = 0.0f;
-    double f = 1.0;
-    if (valid) {
-      z = zv[base + s];
-      dist = (s + 1 < N) ? zv[base + s + 1] - z : 1e-3f;
-      sg = sigma[base + s];
-      e = expf_rn(-sg * dist);
-      alpha = 1.0f - e;
-      fs = (1.0f - alpha) + 1e-10f;
-      f = (double)fs;
-    }
-    double incl = f;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const double up = __shfl_up(incl, off);
-      if (lane >= off) incl *= up;
-    }
-    double excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 1.0;
-    const double T = carry_chunk[c] * excl;
-    const float w = alpha * (float)T;                      // the forward's weight (composite.hip)
-    double dw = 0.0;
-    if (valid) {
-      const int64_t e3 = 3 * (base + s);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        dw += (double)g[k] * (double)rgb[e3 + k];
-        drgb[e3 + k] = w * g[k];
-      }
-      if (gd != 0.0f) dw += (double)gd * ((double)z - dmean) * dinv;
-    }
-    // exclusive suffix sum of dw*w inside the chunk, plus the chunks after it
-    double v = valid ? dw * ((double)alpha * T) : 0.0;
-    double incl_rev = v;                                   // inclusive suffix within the chunk
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const double dn = __shfl_down(incl_rev, off);
-      if (lane + off < 64) incl_rev += dn;
-    }
-    const double excl_rev = incl_rev - v + suffix;
-    if (valid) {
-      const double da = dw * T - excl_rev / (double)fs;
-      dsigma[base + s] = (float)(da * (double)dist * (double)e);
-    }
-    suffix += __shfl(incl_rev, 0);
-  }
-}
-
-int launch_composite_backward(const float* rgb, const float* sigma, const float* z, const float* rgb_map,
-                              const float* target, const float* grad_map, const float* grad_depth, int64_t B, int N,
-                              float scale, float* dsigma, float* drgb, float* sq_err, hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  hipLaunchKernelGGL(composite_backward_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, rgb, sigma, z,
-                     rgb_map, target, grad_map, grad_depth, B, N, scale, dsigma, drgb, sq_err);
-  return check_launch("composite_backward_kernel");
-}
 
 // ------------------------------------------------------------------- merged composite bwd
 // The backward of composite.hip's MERGED composite (the hierarchical step): position
@@ -181,162 +45,31 @@ int launch_composite_backward(const float* rgb, const float* sigma, const float*
 constexpr int kMergedBwdMaxT = 1280;          // N <= 256, Nf <= 1024 (the resampler's limits)
 constexpr int kMergedBwdChunks = kMergedBwdMaxT / 64;
 
-__global__ void __launch_bounds__(256)
-composite_merged_backward_kernel(const float* __restrict__ rgb_c, const float* __restrict__ sigma_c,
-                                 const float* __restrict__ rgb_f, const float* __restrict__ sigma_f,
-                                 const uint16_t* __restrict__ src, const float* __restrict__ zv,
-                                 const float* __restrict__ rgb_map, const float* __restrict__ target,
-                                 const float* __restrict__ grad_map, const float* __restrict__ grad_depth, int64_t B,
-                                 int N, int Nf, float scale, int accumulate, float* dsigma_c, float* drgb_c,
-                                 float* __restrict__ dsigma_f, float* __restrict__ drgb_f,
-                                 float* __restrict__ sq_err) {
-  extern __shared__ f32x4 quads[];    // [rays per block][T]
-  __shared__ double carry_lds[4][kMergedBwdChunks];   // T at each chunk start
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t r = (int64_t)blockIdx.x * ((int)blockDim.x >> 6) + wid;
-  if (r >= B) return;                 // (no block-wide barrier below: a wave owns its ray's LDS)
-  const int T = N + Nf;
-  const int64_t base = r * T, base_c = r * N, base_f = r * Nf;
-  f32x4* rq = quads + wid * T;
-  for (int e = lane; e < T; e += 64) {
-    const bool crs = e < N;
-    const int64_t at = crs ? base_c + e : base_f + (e - N);
-    const float* cs = crs ? rgb_c : rgb_f;
-    rq[e] = f32x4{cs[3 * at], cs[3 * at + 1], cs[3 * at + 2], (crs ? sigma_c : sigma_f)[at]};
-  }
-  float g[3], se = 0.0f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if (target) {
-      const float e = rgb_map[3 * r + c] - target[3 * r + c];
-      g[c] = scale * e;
-      se += e * e;
-    } else {
-      g[c] = grad_map ? grad_map[3 * r + c] : 0.0f;
-    }
-  }
-  const float gd = grad_depth ? grad_depth[r] : 0.0f;
-  if (lane == 0 && sq_err) sq_err[r] = se;
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  // pass 1 (forward order) and pass 2 (reverse order) as in composite_backward_kernel
-  const int nchunk = (T + 63) / 64;
-  double* carry_chunk = carry_lds[wid];
-  double carry = 1.0, wz = 0.0, ws = 0.0;
-  for (int c = 0; c < nchunk; ++c) {
-    const int s = c * 64 + lane;
-    double f = 1.0;
-    float alpha = 0.0f, z = 0.0f;
-    if (s < T) {
-      z = zv[base + s];
-      const float dist = (s + 1 < T) ? zv[base + s + 1] - z : 1e-3f;
-      alpha = 1.0f - expf_rn(-rq[src[base + s]][3] * dist);
-      f = (double)((1.0f - alpha) + 1e-10f);
-    }
-    double incl = f;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const double up = __shfl_up(incl, off);
-      if (lane >= off) incl *= up;
-    }
-    if (gd != 0.0f) {
-      double excl = __shfl_up(incl, 1);
-      if (lane == 0) excl = 1.0;
-      const double w = (double)alpha * (carry * excl);
-      wz += w * (double)z;
-      ws += w;
-    }
-    if (lane == 0) carry_chunk[c] = carry;
-    carry *= __shfl(incl, 63);
-  }
-  double dinv = 0.0, dmean = 0.0;    // 1 / (A + 1e-10), S / (A + 1e-10)
-  if (gd != 0.0f) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      wz += __shfl_xor(wz, off);
-      ws += __shfl_xor(ws, off);
-    }
-    const double den = ws + (double)1e-10f;
-    dinv = 1.0 / den;
-    dmean = wz * dinv;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  double suffix = 0.0;                // sum_{t > current chunk} dw_t w_t
-  for (int c = nchunk - 1; c >= 0; --c) {
-    const int s = c * 64 + lane;
-    const bool valid = s < T;
-    float alpha = 0.0f, dist = 0.0f, e = 1.0f, fs = 1.0f, z = 0.0f;
-    double f = 1.0;
-    int at = 0;                       // the sample's cat index
-    f32x4 q = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (valid) {
-      z = zv[base + s];
-      dist = (s + 1 < T) ? zv[base + s + 1] - z : 1e-3f;
-      at = (int)src[base + s];
-      q = rq[at];
-      e = expf_rn(-q[3] * dist);
-      alpha = 1.0f - e;
-      fs = (1.0f - alpha) + 1e-10f;
-      f = (double)fs;
-    }
-    double incl = f;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const double up = __shfl_up(incl, off);
-      if (lane >= off) incl *= up;
-    }
-    double excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 1.0;
-    const double Tr = carry_chunk[c] * excl;
-    const float w = alpha * (float)Tr;                     // the forward's weight (composite.hip)
-    double dw = 0.0;
-    f32x4 out = {0.0f, 0.0f, 0.0f, 0.0f};                  // (drgb, dsigma)
-    if (valid) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        dw += (double)g[k] * (double)q[k];
-        out[k] = w * g[k];
-      }
-      if (gd != 0.0f) dw += (double)gd * ((double)z - dmean) * dinv;
-    }
-    double v = valid ? dw * ((double)alpha * Tr) : 0.0;
-    double incl_rev = v;                                   // inclusive suffix within the chunk
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const double dn = __shfl_down(incl_rev, off);
-      if (lane + off < 64) incl_rev += dn;
-    }
-    const double excl_rev = incl_rev - v + suffix;
-    if (valid) {
-      const double da = dw * Tr - excl_rev / (double)fs;
-      out[3] = (float)(da * (double)dist * (double)e);
-      rq[at] = out;
-    }
-    suffix += __shfl(incl_rev, 0);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  for (int e = lane; e < T; e += 64) {
-    const f32x4 q = rq[e];
-    if (e < N) {
-      const int64_t at = base_c + e;
-      if (accumulate) {
-        dsigma_c[at] = dsigma_c[at] + q[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) drgb_c[3 * at + k] = drgb_c[3 * at + k] + q[k];
-      } else {
-        dsigma_c[at] = q[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) drgb_c[3 * at + k] = q[k];
-      }
-    } else {
-      const int64_t at = base_f + (e - N);
-      dsigma_f[at] = q[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) drgb_f[3 * at + k] = q[k];
-    }
-  }
+#define COMPOSITE_BWD_ACC 0   // (the kernels, twice: composite_bwd_body.h)
+#include "composite_bwd_body.h"
+#undef COMPOSITE_BWD_ACC
+#define COMPOSITE_BWD_ACC 1
+#include "composite_bwd_body.h"
+#undef COMPOSITE_BWD_ACC
+
+int launch_composite_backward(const float* rgb, const float* sigma, const float* z, const float* rgb_map,
+                              const float* target, const float* grad_map, const float* grad_depth, int64_t B, int N,
+                              float scale, float* dsigma, float* drgb, float* sq_err, hipStream_t s) {
+  if (B == 0) return NERF_OK;
+  hipLaunchKernelGGL(composite_backward_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, rgb, sigma, z,
+                     rgb_map, target, grad_map, grad_depth, B, N, scale, dsigma, drgb, sq_err);
+  return check_launch("composite_backward_kernel");
+}
+
+// the gradient form with an opacity gradient g_acc (nullable) and the forward's background depth bd (NaN: none)
+int launch_composite_backward_acc(const float* rgb, const float* sigma, const float* z, const float* grad_map,
+                                  const float* grad_depth, const float* g_acc, float bd, int64_t B, int N,
+                                  float* dsigma, float* drgb, hipStream_t s) {
+  if (B == 0) return NERF_OK;
+  hipLaunchKernelGGL(composite_backward_acc_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, rgb, sigma, z,
+                     (const float*)nullptr, (const float*)nullptr, grad_map, grad_depth, B, N, 0.0f, dsigma, drgb,
+                     (float*)nullptr, g_acc, bd);
+  return check_launch("composite_backward_acc_kernel");
 }
 
 int launch_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f,
@@ -355,6 +88,77 @@ int launch_composite_merged_backward(const float* rgb_c, const float* sigma_c, c
                      rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, rgb_map, target, grad_map, grad_depth, B, N, Nf, scale,
                      accumulate, dsigma_c, drgb_c, dsigma_f, drgb_f, sq_err);
   return check_launch("composite_merged_backward_kernel");
+}
+
+int launch_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                                         const float* sigma_f, const uint16_t* src, const float* z_all,
+                                         const float* grad_map, const float* grad_depth, const float* g_acc, float bd,
+                                         int64_t B, int N, int Nf, int accumulate, float* dsigma_c, float* drgb_c,
+                                         float* dsigma_f, float* drgb_f, hipStream_t s) {
+  if (B == 0) return NERF_OK;
+  const int T = N + Nf;
+  if (N < 1 || Nf < 1 || T > kMergedBwdMaxT)
+    return set_error(NERF_ERR_UNSUPPORTED, "composite_merged_backward: N=%d Nf=%d (N + Nf <= %d)", N, Nf, kMergedBwdMaxT);
+  const int rpb = T <= 768 ? 4 : 2;   // rays per block: at most 48 KB of LDS
+  const size_t lds = (size_t)rpb * T * sizeof(f32x4);
+  hipLaunchKernelGGL(composite_merged_backward_acc_kernel, dim3((unsigned)((B + rpb - 1) / rpb)), dim3(64 * rpb), lds, s,
+                     rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, (const float*)nullptr, (const float*)nullptr, grad_map,
+                     grad_depth, B, N, Nf, 0.0f, accumulate, dsigma_c, drgb_c, dsigma_f, drgb_f, (float*)nullptr, g_acc,
+                     bd);
+  return check_launch("composite_merged_backward_acc_kernel");
+}
+
+// ------------------------------------------------------------- background loss
+// The per-ray head of a training step with a background: one thread per ray, from the forward's
+// rgb_map, the recomputed opacity acc, the target colour, its alpha (nullable = 1) and the background
+// colour (bg null = black; stride 0: one colour, 3: one per ray), with k = max(0, 1 - acc):
+//   target' = alpha target + (1 - alpha) bg      final = rgb_map + k bg   (composite_bg_kernel's blend)
+//   g_rgb   = scale_rgb (final - target')        scale_rgb = 2 / (3B)
+//   g_acc   = -(bg . g_rgb) where k > 0, else 0, + acc_weight scale_acc (acc - alpha), scale_acc = 2 / B
+//   sq_rgb  = sum_c (final - target')^2          sq_acc = (acc - alpha)^2
+// every product and sum rounded on its own.  Each output has one writer; the two means are reduced by
+// loss_kernel / loss_rays_kernel (adam.hip) in their fixed order: deterministic, no float atomics.
+__global__ void __launch_bounds__(256)
+bg_loss_kernel(const float* __restrict__ rgb_map, const float* __restrict__ acc, const float* __restrict__ target,
+               const float* __restrict__ alpha, const float* __restrict__ bg, int bg_stride, float acc_weight,
+               float scale_rgb, float scale_acc, int64_t B, float* __restrict__ g_rgb, float* __restrict__ g_acc,
+               float* __restrict__ sq_rgb, float* __restrict__ sq_acc, float* __restrict__ rgb_final) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= B) return;
+  const float a = alpha ? alpha[r] : 1.0f;
+  const float ac = acc[r];
+  const float kb = fmaxf(0.0f, 1.0f - ac);
+  const float ia = 1.0f - a;
+  float dot = 0.0f, se = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float b = bg ? bg[(int64_t)bg_stride * r + c] : 0.0f;
+    const float t1 = a * target[3 * r + c], t2 = ia * b;
+    const float tp = t1 + t2;
+    const float kbg = kb * b;
+    const float fin = rgb_map[3 * r + c] + kbg;
+    const float e = fin - tp;
+    const float g = scale_rgb * e;
+    const float ee = e * e, bgg = b * g;
+    se = se + ee;
+    dot = dot + bgg;
+    g_rgb[3 * r + c] = g;
+    if (rgb_final) rgb_final[3 * r + c] = fin;
+  }
+  const float ea = ac - a;
+  const float ga_o = acc_weight * (scale_acc * ea);
+  g_acc[r] = (kb > 0.0f ? -dot : 0.0f) + ga_o;
+  sq_rgb[r] = se;
+  sq_acc[r] = ea * ea;
+}
+
+int launch_bg_loss(const float* rgb_map, const float* acc, const float* target, const float* alpha, const float* bg,
+                   int bg_stride, float acc_weight, float scale_rgb, float scale_acc, int64_t B, float* g_rgb,
+                   float* g_acc, float* sq_rgb, float* sq_acc, float* rgb_final, hipStream_t s) {
+  if (B == 0) return NERF_OK;
+  hipLaunchKernelGGL(bg_loss_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, rgb_map, acc, target, alpha, bg,
+                     bg_stride, acc_weight, scale_rgb, scale_acc, B, g_rgb, g_acc, sq_rgb, sq_acc, rgb_final);
+  return check_launch("bg_loss_kernel");
 }
 
 // dst[i] += src[i] over up to 25 segments (the hierarchical step's second gradient set into the

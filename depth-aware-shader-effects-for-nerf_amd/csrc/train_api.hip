@@ -176,6 +176,55 @@ static bool last_forward(const void* ws, ForwardRecord& r) {
   r = it->second;
   return true;
 }
+// ---- the backward's head with a background (include/nerfmi_train.h "background")
+// The _bg entries' additions.  Off (no alpha, no background, acc_weight 0): the original entry's calls.
+struct BgLoss {
+  const float* alpha;
+  const float* bg;
+  int64_t bg_rows;
+  double acc_weight;
+  bool off() const { return !alpha && bg_rows == 0 && acc_weight == 0.0; }
+};
+
+static int check_bg_loss(const char* fn, const BgLoss& o, int64_t B) {
+  REQUIRE(o.bg_rows == 0 || o.bg_rows == 1 || o.bg_rows == B, "%s: bg_rows=%lld with B=%lld (0, 1 or B)", fn,
+          (long long)o.bg_rows, (long long)B);
+  REQUIRE(o.bg_rows == 0 || o.bg, "%s: null bg with bg_rows=%lld", fn, (long long)o.bg_rows);
+  REQUIRE(o.acc_weight >= 0.0 && o.acc_weight <= 3.0e38, "%s: acc_weight=%g (>= 0)", fn, o.acc_weight);   // (NaN fails)
+  return NERF_OK;
+}
+
+// Per-ray scratch of the head: the head of the sample set's gradient rows, which nothing holds until
+// launch_mlp_backward writes them after the head (stream order).  Its 6 x roundup64(B) floats always
+// fit: a set's rows are at least 32 x kGradRow floats and at least kGradRow per ray.
+struct BgScratch {
+  float *acc, *g_rgb, *g_acc, *sq_acc;
+};
+static BgScratch bg_scratch(float* grad_rows, int64_t B) {
+  const size_t b = ((size_t)B + 63) & ~(size_t)63;
+  return BgScratch{grad_rows, grad_rows + b, grad_rows + 4 * b, grad_rows + 5 * b};
+}
+static_assert(kGradRow >= 6 * 64, "the head's per-ray scratch fits in a ray's gradient rows");
+
+// One sample set's head from its per-ray gradient (g_rgb, g_acc) and the two means; `composite_acc`
+// recomputes the opacity of the rows the forward left (its maps go to the set's unused `maps` region),
+// `composite_backward` is the set's composite backward in its _acc form.
+template <typename Acc, typename Bwd>
+static int backward_head_bg(const TrainWs& w, const float* rgb_map, const float* target, int64_t B, const BgLoss& o,
+                            double weight, float* loss_rgb, float* loss_acc, float* rgb_final, Acc&& composite_acc,
+                            Bwd&& composite_backward, hipStream_t s) {
+  const BgScratch t = bg_scratch(w.grad, B);
+  const CompositeBg acc_only{nullptr, 0, __builtin_nanf(""), t.acc};
+  int rc;
+  if ((rc = composite_acc(w.maps, w.maps + 3 * B, acc_only))) return rc;
+  if ((rc = launch_bg_loss(rgb_map, t.acc, target, o.alpha, o.bg_rows ? o.bg : nullptr, o.bg_rows > 1 ? 3 : 0,
+                           (float)o.acc_weight, (float)(weight * 2.0 / (3.0 * (double)B)),
+                           (float)(weight * 2.0 / (double)B), B, t.g_rgb, t.g_acc, w.sq_err, t.sq_acc, rgb_final, s)))
+    return rc;
+  if ((rc = composite_backward(t.g_rgb, t.g_acc))) return rc;
+  if ((rc = launch_loss(w.sq_err, B, loss_rgb, s))) return rc;
+  return launch_loss_rays(t.sq_acc, B, loss_acc, s);
+}
 }  // namespace nerf
 
 using namespace nerf;
@@ -544,6 +593,32 @@ static int backward_head(const TrainWs& w, const float* rgb_map, const float* ta
   return launch_loss(w.sq_err, B, loss, s);
 }
 
+// the dense rows' head (nerf_train_backward_bg and, on the zero-filled dense rows, the occupancy one)
+static int backward_head_dense_bg(const TrainWs& w, const float* rgb_map, const float* target, int64_t B, int N,
+                                  const BgLoss& o, float* loss, float* rgb_final, hipStream_t s) {
+  return backward_head_bg(
+      w, rgb_map, target, B, o, 1.0, loss, loss + 1, rgb_final,
+      [&](float* m_rgb, float* m_depth, const CompositeBg& a) {
+        return launch_composite_bg(w.rgb, w.sigma, w.z, B, N, m_rgb, m_depth, nullptr, a, s);
+      },
+      [&](const float* g_rgb, const float* g_acc) {
+        return launch_composite_backward_acc(w.rgb, w.sigma, w.z, g_rgb, nullptr, g_acc, __builtin_nanf(""), B, N, w.dsigma,
+                                             w.drgb, s);
+      },
+      s);
+}
+
+// with every option off: the opacity parts of the loss read 0 and rgb_final is rgb_map
+static int bg_off_outputs(const char* fn, float* loss_acc, int n_acc, float* rgb_final, const float* rgb_map, int64_t B,
+                          hipStream_t s) {
+  if (hipMemsetAsync(loss_acc, 0, (size_t)n_acc * 4, s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
+  if (rgb_final && B > 0 &&
+      hipMemcpyAsync(rgb_final, rgb_map, (size_t)B * 12, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "%s: rgb_final copy failed", fn);
+  return NERF_OK;
+}
+
 size_t nerf_train_workspace_bytes(int64_t B, int N) {
   if (B < 0 || N < 1) return 0;
   TrainWs w;
@@ -584,32 +659,57 @@ int nerf_train_forward(const float* packed, const float* rays_o, const float* ra
   return forward_tail("nerf_train_forward", w, B, N, rgb_map, depth_map, weights_out, z_out, s);
 }
 
-int nerf_train_backward(const float* packed, const float* packedT, const float* rgb_map, const float* target,
-                        int64_t B, int N, const float* app, int64_t app_rows, float* const* param_grads_out,
-                        float* dapp, float* loss, void* workspace, size_t ws_bytes, nerf_stream_t stream) {
-  REQUIRE(B >= 0 && N >= 1 && N <= 4096, "nerf_train_backward: B=%lld N=%d", (long long)B, N);
-  REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "nerf_train_backward: app_rows=%lld", (long long)app_rows);
+// nerf_train_backward (bgl null) and nerf_train_backward_bg
+static int train_backward(const char* fn, const float* packed, const float* packedT, const float* rgb_map,
+                          const float* target, int64_t B, int N, const float* app, int64_t app_rows,
+                          float* const* param_grads_out, float* dapp, float* loss, void* workspace, size_t ws_bytes,
+                          const BgLoss* bgl, float* rgb_final, nerf_stream_t stream) {
+  REQUIRE(B >= 0 && N >= 1 && N <= 4096, "%s: B=%lld N=%d", fn, (long long)B, N);
+  REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "%s: app_rows=%lld", fn, (long long)app_rows);
   int rc;
-  if ((rc = check_backward_ptrs("nerf_train_backward", packed, packedT, rgb_map, target, B, app, app_rows,
-                                param_grads_out, loss, workspace)))
+  if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
+  if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
+                                workspace)))
     return rc;
   if (B == 0) return NERF_OK;
   TrainWs w;
-  if ((rc = train_ws("nerf_train_backward", B, N, false, workspace, ws_bytes, w))) return rc;
+  if ((rc = train_ws(fn, B, N, false, workspace, ws_bytes, w))) return rc;
   hipStream_t s = (hipStream_t)stream;
   // the mask rows exist only when this workspace's forward ran under f16x3; the backward's kernels
   // follow the arithmetic in force now (an f16x3 backward after an f32 forward reads the ReLU masks
   // from the saved activations instead)
   ForwardRecord fwd;
   if (!last_forward(workspace, fwd) || fwd.kind != kStepDense)
-    return set_error(NERF_ERR_BAD_ARG, "nerf_train_backward: no nerf_train_forward wrote this workspace");
+    return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_forward wrote this workspace", fn);
   const uint32_t* masks = fwd.arith == NERF_ARITH_F16X3 ? w.masks : nullptr;
   const int64_t M = B * N;
-  if ((rc = backward_head(w, rgb_map, target, B, N, loss, s))) return rc;
+  if (bgl && !bgl->off()) {
+    if ((rc = backward_head_dense_bg(w, rgb_map, target, B, N, *bgl, loss, rgb_final, s))) return rc;
+  } else {
+    if ((rc = backward_head(w, rgb_map, target, B, N, loss, s))) return rc;
+    if (bgl && (rc = bg_off_outputs(fn, loss + 1, 1, rgb_final, rgb_map, B, s))) return rc;
+  }
   if ((rc = launch_mlp_backward(packed, packedT, w.save, masks, w.sigma, w.rgb, w.dsigma, w.drgb, M, w.grad, s,
                                 /*store_dhd=*/!fused_ray_sums(N))))
     return rc;
   return param_grads(w.save, w.grad, M, N, app, app_rows, packed, param_grads_out, dapp, w.wgrad, w.wgrad_floats, s);
+}
+
+int nerf_train_backward(const float* packed, const float* packedT, const float* rgb_map, const float* target,
+                        int64_t B, int N, const float* app, int64_t app_rows, float* const* param_grads_out,
+                        float* dapp, float* loss, void* workspace, size_t ws_bytes, nerf_stream_t stream) {
+  return train_backward("nerf_train_backward", packed, packedT, rgb_map, target, B, N, app, app_rows, param_grads_out,
+                        dapp, loss, workspace, ws_bytes, nullptr, nullptr, stream);
+}
+
+int nerf_train_backward_bg(const float* packed, const float* packedT, const float* rgb_map, const float* target,
+                           int64_t B, int N, const float* app, int64_t app_rows, float* const* param_grads_out,
+                           float* dapp, float* loss, void* workspace, size_t ws_bytes, const float* alpha,
+                           const float* bg, int64_t bg_rows, double acc_weight, float* rgb_final,
+                           nerf_stream_t stream) {
+  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  return train_backward("nerf_train_backward_bg", packed, packedT, rgb_map, target, B, N, app, app_rows,
+                        param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream);
 }
 
 int nerf_train_occ_sample(const float* rays_o, const float* rays_d, int64_t B, double near, double far, int N,
@@ -652,30 +752,38 @@ int nerf_train_occ_forward(const float* packed, const float* rays_o, int64_t B, 
   return forward_tail("nerf_train_occ_forward", w, B, N, rgb_map, depth_map, weights_out, z_out, s);
 }
 
-int nerf_train_occ_backward(const float* packed, const float* packedT, const float* rgb_map, const float* target,
-                            int64_t B, int N, int64_t M_live, const float* app, int64_t app_rows,
-                            float* const* param_grads_out, float* dapp, float* loss, void* workspace, size_t ws_bytes,
-                            nerf_stream_t stream) {
+// nerf_train_occ_backward (bgl null) and nerf_train_occ_backward_bg
+static int train_occ_backward(const char* fn, const float* packed, const float* packedT, const float* rgb_map,
+                              const float* target, int64_t B, int N, int64_t M_live, const float* app,
+                              int64_t app_rows, float* const* param_grads_out, float* dapp, float* loss,
+                              void* workspace, size_t ws_bytes, const BgLoss* bgl, float* rgb_final,
+                              nerf_stream_t stream) {
   int rc;
-  if ((rc = check_occ_step("nerf_train_occ_backward", "step", B, N, M_live, app_rows))) return rc;
-  if ((rc = check_backward_ptrs("nerf_train_occ_backward", packed, packedT, rgb_map, target, B, app, app_rows,
-                                param_grads_out, loss, workspace)))
+  if ((rc = check_occ_step(fn, "step", B, N, M_live, app_rows))) return rc;
+  if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
+  if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
+                                workspace)))
     return rc;
   if (B == 0) return NERF_OK;
   TrainWs w;
-  if ((rc = train_ws("nerf_train_occ_backward", B, N, true, workspace, ws_bytes, w))) return rc;
+  if ((rc = train_ws(fn, B, N, true, workspace, ws_bytes, w))) return rc;
   ForwardRecord fwd;
   if (!last_forward(workspace, fwd) || fwd.kind != kStepOcc || fwd.M_live != M_live)
-    return set_error(NERF_ERR_BAD_ARG, "nerf_train_occ_backward: no nerf_train_occ_forward with M_live=%lld wrote this "
-                     "workspace", (long long)M_live);
+    return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_occ_forward with M_live=%lld wrote this "
+                     "workspace", fn, (long long)M_live);
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = backward_head(w, rgb_map, target, B, N, loss, s))) return rc;
+  if (bgl && !bgl->off()) {   // (on the dense zero-filled rows: a dead sample has weight 0)
+    if ((rc = backward_head_dense_bg(w, rgb_map, target, B, N, *bgl, loss, rgb_final, s))) return rc;
+  } else {
+    if ((rc = backward_head(w, rgb_map, target, B, N, loss, s))) return rc;
+    if (bgl && (rc = bg_off_outputs(fn, loss + 1, 1, rgb_final, rgb_map, B, s))) return rc;
+  }
   if (M_live == 0) {   // every sample dead: sigma = 0 is a constant of the step, every gradient is zero
     for (int p = 0; p < P_COUNT; ++p)
       if (hipMemsetAsync(param_grads_out[p], 0, param_floats(p) * 4, s) != hipSuccess)
-        return set_error(NERF_ERR_HIP, "nerf_train_occ_backward: hipMemsetAsync failed");
+        return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
     if (dapp && app_rows && hipMemsetAsync(dapp, 0, (size_t)kAppDim * 4, s) != hipSuccess)
-      return set_error(NERF_ERR_HIP, "nerf_train_occ_backward: hipMemsetAsync failed");
+      return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
     return NERF_OK;
   }
   if ((rc = launch_occ_gather_grads(w.dsigma, w.drgb, w.live, M_live, w.dsigma_live, w.drgb_live, s))) return rc;
@@ -684,6 +792,24 @@ int nerf_train_occ_backward(const float* packed, const float* packedT, const flo
     return rc;
   return param_grads(w.save, w.grad, M_live, 1, app, app_rows, packed, param_grads_out, dapp, w.wgrad,
                      w.wgrad_floats, s);
+}
+
+int nerf_train_occ_backward(const float* packed, const float* packedT, const float* rgb_map, const float* target,
+                            int64_t B, int N, int64_t M_live, const float* app, int64_t app_rows,
+                            float* const* param_grads_out, float* dapp, float* loss, void* workspace, size_t ws_bytes,
+                            nerf_stream_t stream) {
+  return train_occ_backward("nerf_train_occ_backward", packed, packedT, rgb_map, target, B, N, M_live, app, app_rows,
+                            param_grads_out, dapp, loss, workspace, ws_bytes, nullptr, nullptr, stream);
+}
+
+int nerf_train_occ_backward_bg(const float* packed, const float* packedT, const float* rgb_map, const float* target,
+                               int64_t B, int N, int64_t M_live, const float* app, int64_t app_rows,
+                               float* const* param_grads_out, float* dapp, float* loss, void* workspace,
+                               size_t ws_bytes, const float* alpha, const float* bg, int64_t bg_rows,
+                               double acc_weight, float* rgb_final, nerf_stream_t stream) {
+  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  return train_occ_backward("nerf_train_occ_backward_bg", packed, packedT, rgb_map, target, B, N, M_live, app, app_rows,
+                            param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream);
 }
 
 // ------------------------------------------------------------- the hierarchical step
@@ -750,13 +876,16 @@ int nerf_train_hier_forward(const float* packed, const float* rays_o, const floa
   return NERF_OK;
 }
 
-int nerf_train_hier_backward(const float* packed, const float* packedT, const float* rgb_map, const float* coarse_rgb,
-                             const float* target, int64_t B, int N, int Nf, double coarse_weight, const float* app,
-                             int64_t app_rows, float* const* param_grads_out, float* dapp, float* loss,
-                             void* workspace, size_t ws_bytes, nerf_stream_t stream) {
-  const char* fn = "nerf_train_hier_backward";
+// nerf_train_hier_backward (bgl null) and nerf_train_hier_backward_bg
+static int train_hier_backward(const char* fn, const float* packed, const float* packedT, const float* rgb_map,
+                               const float* coarse_rgb, const float* target, int64_t B, int N, int Nf,
+                               double coarse_weight, const float* app, int64_t app_rows,
+                               float* const* param_grads_out, float* dapp, float* loss, void* workspace,
+                               size_t ws_bytes, const BgLoss* bgl, float* rgb_final, float* coarse_final,
+                               nerf_stream_t stream) {
   int rc;
   if ((rc = check_hier_shape(fn, B, N, Nf))) return rc;
+  if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
   REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "%s: app_rows=%lld", fn, (long long)app_rows);
   REQUIRE(coarse_weight >= 0.0 && coarse_weight <= 3.0e38, "%s: coarse_weight=%g", fn, coarse_weight);
   if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
@@ -774,15 +903,49 @@ int nerf_train_hier_backward(const float* packed, const float* packedT, const fl
   const bool f16 = fwd.arith == NERF_ARITH_F16X3;
   const double mse_scale = 2.0 / (3.0 * (double)B);
   // the coarse composite's term, then the merged composite's on top of it in the coarse rows
-  if ((rc = launch_composite_backward(c.rgb, c.sigma, c.z, coarse_rgb, target, nullptr, nullptr, B, N,
-                                      (float)(coarse_weight * mse_scale), c.dsigma, c.drgb, c.sq_err, s)))
-    return rc;
-  if ((rc = launch_composite_merged_backward(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, rgb_map, target, nullptr,
-                                             nullptr, B, N, Nf, (float)mse_scale, 1, c.dsigma, c.drgb, f.dsigma, f.drgb,
-                                             f.sq_err, s)))
-    return rc;
-  if ((rc = launch_loss(f.sq_err, B, loss, s))) return rc;
-  if ((rc = launch_loss(c.sq_err, B, loss + 1, s))) return rc;
+  if (bgl && !bgl->off()) {
+    // the same two terms from each part's per-ray head (the coarse part's scaled by coarse_weight); loss:
+    // fine colour, coarse colour, fine opacity, coarse opacity
+    const float nan = __builtin_nanf("");
+    if ((rc = backward_head_bg(
+             c, coarse_rgb, target, B, *bgl, coarse_weight, loss + 1, loss + 3, coarse_final,
+             [&](float* m_rgb, float* m_depth, const CompositeBg& a) {
+               return launch_composite_bg(c.rgb, c.sigma, c.z, B, N, m_rgb, m_depth, nullptr, a, s);
+             },
+             [&](const float* g_rgb, const float* g_acc) {
+               return launch_composite_backward_acc(c.rgb, c.sigma, c.z, g_rgb, nullptr, g_acc, nan, B, N, c.dsigma,
+                                                    c.drgb, s);
+             },
+             s)))
+      return rc;
+    if ((rc = backward_head_bg(
+             f, rgb_map, target, B, *bgl, 1.0, loss, loss + 2, rgb_final,
+             [&](float* m_rgb, float* m_depth, const CompositeBg& a) {
+               return launch_composite_merged_bg(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, B, N, Nf, m_rgb, m_depth,
+                                                 nullptr, a, s);
+             },
+             [&](const float* g_rgb, const float* g_acc) {
+               return launch_composite_merged_backward_acc(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, g_rgb, nullptr,
+                                                           g_acc, nan, B, N, Nf, 1, c.dsigma, c.drgb, f.dsigma, f.drgb,
+                                                           s);
+             },
+             s)))
+      return rc;
+  } else {
+    if ((rc = launch_composite_backward(c.rgb, c.sigma, c.z, coarse_rgb, target, nullptr, nullptr, B, N,
+                                        (float)(coarse_weight * mse_scale), c.dsigma, c.drgb, c.sq_err, s)))
+      return rc;
+    if ((rc = launch_composite_merged_backward(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, rgb_map, target,
+                                               nullptr, nullptr, B, N, Nf, (float)mse_scale, 1, c.dsigma, c.drgb,
+                                               f.dsigma, f.drgb, f.sq_err, s)))
+      return rc;
+    if ((rc = launch_loss(f.sq_err, B, loss, s))) return rc;
+    if ((rc = launch_loss(c.sq_err, B, loss + 1, s))) return rc;
+    if (bgl) {
+      if ((rc = bg_off_outputs(fn, loss + 2, 2, rgb_final, rgb_map, B, s))) return rc;
+      if ((rc = bg_off_outputs(fn, loss + 2, 2, coarse_final, coarse_rgb, B, s))) return rc;
+    }
+  }
   // the fine part's gradients go to the workspace's second set
   float* g2[P_COUNT];
   size_t at = 0;
@@ -814,6 +977,52 @@ int nerf_train_hier_backward(const float* packed, const float* packedT, const fl
   }
   if (dapp && app_rows) dst[count] = dapp, src[count] = h.dapp2, n[count] = (size_t)app_rows * kAppDim, ++count;
   return launch_add_segments(dst, src, n, count, s);
+}
+
+int nerf_train_hier_backward(const float* packed, const float* packedT, const float* rgb_map, const float* coarse_rgb,
+                             const float* target, int64_t B, int N, int Nf, double coarse_weight, const float* app,
+                             int64_t app_rows, float* const* param_grads_out, float* dapp, float* loss,
+                             void* workspace, size_t ws_bytes, nerf_stream_t stream) {
+  return train_hier_backward("nerf_train_hier_backward", packed, packedT, rgb_map, coarse_rgb, target, B, N, Nf,
+                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, nullptr,
+                             nullptr, nullptr, stream);
+}
+
+int nerf_train_hier_backward_bg(const float* packed, const float* packedT, const float* rgb_map,
+                                const float* coarse_rgb, const float* target, int64_t B, int N, int Nf,
+                                double coarse_weight, const float* app, int64_t app_rows,
+                                float* const* param_grads_out, float* dapp, float* loss, void* workspace,
+                                size_t ws_bytes, const float* alpha, const float* bg, int64_t bg_rows,
+                                double acc_weight, float* rgb_final, float* coarse_final, nerf_stream_t stream) {
+  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  return train_hier_backward("nerf_train_hier_backward_bg", packed, packedT, rgb_map, coarse_rgb, target, B, N, Nf,
+                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, &o,
+                             rgb_final, coarse_final, stream);
+}
+
+int nerf_composite_backward_grad_acc(const float* rgb, const float* sigma, const float* z_vals,
+                                     const float* grad_rgb_map, const float* grad_depth_map, int64_t B, int N,
+                                     float* dsigma, float* drgb, const float* g_acc, float bd, nerf_stream_t stream) {
+  REQUIRE(B >= 0, "nerf_composite_backward_grad_acc: B=%lld", (long long)B);
+  if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward_grad_acc: N=%d (1..4096)", N);
+  REQUIRE(B == 0 || (rgb && sigma && z_vals && dsigma && drgb), "nerf_composite_backward_grad_acc: null pointer");
+  return launch_composite_backward_acc(rgb, sigma, z_vals, grad_rgb_map, grad_depth_map, g_acc, bd, B, N, dsigma, drgb,
+                                       (hipStream_t)stream);
+}
+
+int nerf_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                                       const float* sigma_f, const uint16_t* src, const float* z_all,
+                                       const float* grad_rgb_map, const float* grad_depth_map, int64_t B, int N, int Nf,
+                                       int accumulate_coarse, float* dsigma_c, float* drgb_c, float* dsigma_f,
+                                       float* drgb_f, const float* g_acc, float bd, nerf_stream_t stream) {
+  REQUIRE(B >= 0, "nerf_composite_merged_backward_acc: B=%lld", (long long)B);
+  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_merged_backward_acc: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
+  REQUIRE(B == 0 || (rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c && drgb_c && dsigma_f && drgb_f),
+          "nerf_composite_merged_backward_acc: null pointer");
+  return launch_composite_merged_backward_acc(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, grad_rgb_map, grad_depth_map,
+                                              g_acc, bd, B, N, Nf, accumulate_coarse, dsigma_c, drgb_c, dsigma_f, drgb_f,
+                                              (hipStream_t)stream);
 }
 
 int nerf_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,

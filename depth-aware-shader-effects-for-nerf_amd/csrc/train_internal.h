@@ -78,6 +78,20 @@ int launch_composite_merged_backward(const float* rgb_c, const float* sigma_c, c
                                      const float* grad_depth, int64_t B, int N, int Nf, float scale, int accumulate,
                                      float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f, float* sq_err,
                                      hipStream_t s);
+// the gradient forms with an opacity gradient g_acc (B, nullable = 0: added to every dw of the ray) and the
+// forward's background depth bd (NaN: the normalised depth): composite_bwd_body.h, DESIGN.md §15
+int launch_composite_backward_acc(const float* rgb, const float* sigma, const float* z, const float* grad_map,
+                                  const float* grad_depth, const float* g_acc, float bd, int64_t B, int N,
+                                  float* dsigma, float* drgb, hipStream_t s);
+int launch_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                                         const float* sigma_f, const uint16_t* src, const float* z_all,
+                                         const float* grad_map, const float* grad_depth, const float* g_acc, float bd,
+                                         int64_t B, int N, int Nf, int accumulate, float* dsigma_c, float* drgb_c,
+                                         float* dsigma_f, float* drgb_f, hipStream_t s);
+// the per-ray loss head of a step with a background (composite_bwd.hip; the means: launch_loss / launch_loss_rays)
+int launch_bg_loss(const float* rgb_map, const float* acc, const float* target, const float* alpha, const float* bg,
+                   int bg_stride, float acc_weight, float scale_rgb, float scale_acc, int64_t B, float* g_rgb,
+                   float* g_acc, float* sq_rgb, float* sq_acc, float* rgb_final, hipStream_t s);
 // dst[k][i] += src[k][i], i < n[k], for count <= 25 segments in one launch
 int launch_add_segments(float* const* dst, const float* const* src, const size_t* n, int count, hipStream_t s);
 // mlp_backward.hip
@@ -99,5 +113,6 @@ int launch_ray_sums(const float* grad, const float* save, int64_t B, int N, floa
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                 double eps, int64_t step, hipStream_t s);
 int launch_loss(const float* sq_err, int64_t B, float* loss, hipStream_t s);
+int launch_loss_rays(const float* sq_err, int64_t B, float* loss, hipStream_t s);   // sum / B
 
 }  // namespace nerf

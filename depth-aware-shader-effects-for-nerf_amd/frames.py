@@ -56,13 +56,16 @@ def shard_rays(ray_fn, H, W, n_frames, start, end):
 def _render_shard(ray_fn, render_fn, H, W, n_frames, start, end, buf):
     if end > start:
         o, d = shard_rays(ray_fn, H, W, n_frames, start, end)
-        rgb, depth = render_fn(o, d, start)
+        rgb, depth, *acc = render_fn(o, d, start)
         buf[: end - start, :3] = rgb.to(buf.device)
-        buf[: end - start, 3:] = depth.reshape(-1, 1).to(buf.device)
+        buf[: end - start, 3:4] = depth.reshape(-1, 1).to(buf.device)
+        if buf.shape[1] > 4:       # the opacity map travels beside the depth
+            buf[: end - start, 4:] = acc[0].reshape(-1, 1).to(buf.device)
 
 
 @torch.no_grad()
-def render_frames_sharded(ray_fn, render_fn, H, W, n_frames, group=None, device=None, virtual_shards=None):
+def render_frames_sharded(ray_fn, render_fn, H, W, n_frames, group=None, device=None, virtual_shards=None,
+                          with_acc=False):
     """Render n_frames HxW frames over the ranks of `group`.
 
     ray_fn(frame, row0, nrows) -> (rays_o, rays_d) for those rows (row-major, (nrows*W, 3));
@@ -72,43 +75,51 @@ def render_frames_sharded(ray_fn, render_fn, H, W, n_frames, group=None, device=
     virtual_shards=G (one process only): render the G shards G ranks would render, one after the
     other, and reassemble them as the all-gather would (the 1-GPU "G virtual shards"
     check of the sharding and reassembly of a G-GPU run).
+    with_acc: render_fn returns (rgb, depth, acc (n,1)) and the opacity map is gathered like the depth:
+    the result is then (rgb, depth, acc (n_frames,H,W)).
     Returns (rgb (n_frames,H,W,3), depth (n_frames,H,W)) on every rank.  Inference only (no autograd
     graph: the outputs are copied into the reassembly buffer, as the reference renders its frames
     under torch.no_grad(), run.py:217).
     """
     world, rank, collective = _world(group)
     total = n_frames * H * W
+    C = 5 if with_acc else 4
     if virtual_shards is not None:
         if world != 1:
             raise ValueError("render_frames_sharded: virtual_shards runs in one process (world size 1)")
         G = int(virtual_shards)
         per = shard_range(total, G, 0)[2]
-        out = torch.zeros(G * per, 4, device=device)
+        out = torch.zeros(G * per, C, device=device)
         for r in range(G):
             start, end, _ = shard_range(total, G, r)
             _render_shard(ray_fn, render_fn, H, W, n_frames, start, end, out[r * per:(r + 1) * per])
     else:
         start, end, per = shard_range(total, world, rank)
-        buf = torch.zeros(per, 4, device=device)
+        buf = torch.zeros(per, C, device=device)
         _render_shard(ray_fn, render_fn, H, W, n_frames, start, end, buf)
         if collective:
-            out = torch.empty(world * per, 4, device=buf.device)
+            out = torch.empty(world * per, C, device=buf.device)
             dist.all_gather_into_tensor(out, buf, group=group)
         else:
             out = buf
-    frames = out[:total].reshape(n_frames, H, W, 4)
+    frames = out[:total].reshape(n_frames, H, W, C)
+    if with_acc:
+        return frames[..., :3], frames[..., 3], frames[..., 4]
     return frames[..., :3], frames[..., 3]
 
 
 @torch.no_grad()
 def render_path_frames(model, poses, H, W, focal, near, far, n_samples, n_importance=0, appearance_embedding=None,
                        perturb=False, hierarchical=False, seed=0, group=None, timing=None, virtual_shards=None,
-                       occupancy=None):
+                       occupancy=None, background=None, background_depth=None, return_acc=False):
     """render_frames_sharded with nerfmi's HIP get_rays / render_rays (one list entry per frame:
     a (3,4)/(4,4) c2w, kept on the host: ray generation takes the pose by value, so no shard
     synchronises on a device-to-host copy).  The in-kernel draws are keyed by `seed` and the global
     ray index, so the frames are bit-identical for every world size.  timing: passed to
-    render_rays (per-launch MLP events); occupancy: an OccupancyGrid, passed to render_rays."""
+    render_rays (per-launch MLP events); occupancy: an OccupancyGrid, passed to render_rays.
+    background (three floats, or one colour per ray of the whole batch of frames, (n_frames*H*W, 3)),
+    background_depth and return_acc go to render_rays with every shard; with return_acc the result is
+    (rgb, depth, acc (n_frames,H,W)), the opacity map gathered like the depth."""
     from . import _lib
     from .ray_utils import rays_on_device
     from .render import render_rays
@@ -118,12 +129,24 @@ def render_path_frames(model, poses, H, W, focal, near, far, n_samples, n_import
     def ray_fn(frame, row0, nrows):
         return rays_on_device(H, W, focal, c2ws[frame], (row0, nrows), dev)
 
+    per_ray_bg = isinstance(background, torch.Tensor) and background.numel() != 3
+    if per_ray_bg and background.numel() != 3 * len(c2ws) * H * W:
+        raise ValueError(f"render_path_frames(background=): expected 3 floats or ({len(c2ws) * H * W},3) colours, "
+                         f"got {tuple(background.shape)}")
+
     def render_fn(o, d, offset):
-        rgb, depth, _ = render_rays(model, o, d, near, far, n_samples, n_importance,
-                                    appearance_embedding=appearance_embedding, perturb=perturb,
-                                    hierarchical=hierarchical, seed=int(seed) & (2 ** 62 - 1), ray_offset=offset,
-                                    timing=timing, **({} if occupancy is None else {"occupancy": occupancy}))
-        return rgb, depth
+        extra = {} if occupancy is None else {"occupancy": occupancy}
+        if background is not None:
+            extra["background"] = background.reshape(-1, 3)[offset: offset + o.shape[0]] if per_ray_bg else background
+        if background_depth is not None:
+            extra["background_depth"] = background_depth
+        if return_acc:
+            extra["return_acc"] = True
+        rgb, depth, ex = render_rays(model, o, d, near, far, n_samples, n_importance,
+                                     appearance_embedding=appearance_embedding, perturb=perturb,
+                                     hierarchical=hierarchical, seed=int(seed) & (2 ** 62 - 1), ray_offset=offset,
+                                     timing=timing, **extra)
+        return (rgb, depth, ex["acc_map"]) if return_acc else (rgb, depth)
 
     return render_frames_sharded(ray_fn, render_fn, H, W, len(c2ws), group=group, device=dev,
-                                 virtual_shards=virtual_shards)
+                                 virtual_shards=virtual_shards, **({"with_acc": True} if return_acc else {}))

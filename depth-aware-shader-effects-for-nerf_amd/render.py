@@ -28,6 +28,19 @@ and ``background_color``.  Keyword-only extras:
                       inference path only: combined with gradients, staged=True or timing= it raises
                       ValueError.  Training with a grid is the Trainer's (train.py,
                       Trainer(occupancy=)), not autograd's.
+  background          three floats or a (B,3) tensor (not a reference feature; ``background_color`` stays
+                      accepted and ignored): the maps are composited over it, rgb_map + k * background
+                      with k = max(0, 1 - acc) and acc the ray's opacity; with
+                      hierarchical=True the coarse maps get the same blend.
+  background_depth    a float: depth_map becomes the expected depth with the background at that depth,
+                      sum w z + k * background_depth (an empty ray's depth is then background_depth
+                      exactly), instead of the normalised sum w z / (sum w + 1e-10).
+  return_acc          extras['acc_map'] (...,1) = the ray's opacity sum w (also present whenever a
+                      background or a background depth is given; 'acc_map_coarse' with hierarchical=True).
+                      The three work plain, hierarchical, with occupancy= and chunked
+                      (nerf_render_rays_bg / nerf_render_rays_occ_bg), and under gradients on the
+                      coarse differentiable path, where acc_map carries a gradient too
+                      (nerf_composite_backward_grad_acc); staged=True and timing= take none of them.
 ``render_rays`` is the same function (the north-star name).
 
 With gradients enabled and a trainable model (or an appearance embedding that requires grad),
@@ -63,8 +76,13 @@ def packed_for(model):
 
 def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, appearance_embedding=None,
                   background_color=None, perturb=True, *, hierarchical=False, t_rand=None, u_rand=None,
-                  seed=None, ray_offset=0, timing=None, staged=False, reuse_coarse=True, occupancy=None):
+                  seed=None, ray_offset=0, timing=None, staged=False, reuse_coarse=True, occupancy=None,
+                  background=None, background_depth=None, return_acc=False):
     from . import autograd
+    bg_on = background is not None or background_depth is not None or bool(return_acc)
+    if bg_on and (staged or timing is not None):
+        raise ValueError(f"nerfmi.volume_render({'staged=True' if staged else 'timing='}) takes no background=, "
+                         f"background_depth= or return_acc=: they run on the single-call path")
     if occupancy is not None:
         from .occupancy import OccupancyGrid
         if not isinstance(occupancy, OccupancyGrid):
@@ -85,7 +103,9 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
                 f"parameters that do not require grad; the coarse call (hierarchical=False) is differentiable, and "
                 f"nerfmi.train.Trainer(hierarchical=True) trains with the fine pass on a coarse + fine loss.")
         return autograd.volume_render_grad(model, rays_o, rays_d, near, far, n_samples, appearance_embedding,
-                                           perturb, t_rand=t_rand, seed=seed, ray_offset=ray_offset)
+                                           perturb, t_rand=t_rand, seed=seed, ray_offset=ray_offset,
+                                           **(dict(background=background, background_depth=background_depth,
+                                                   return_acc=return_acc) if bg_on else {}))
     dev = _lib.device()
     lib = _lib.load()
     orig_shape = rays_o.shape
@@ -112,6 +132,11 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
     if Nf:
         crgb = torch.empty(B, 3, device=dev)
         cdepth = torch.empty(B, 1, device=dev)
+    if bg_on:
+        bg, bg_rows = background_rows(background, B, dev)
+        bd = float("nan") if background_depth is None else float(background_depth)
+        acc = torch.empty(B, 1, device=dev)
+        cacc = torch.empty(B, 1, device=dev) if Nf else None
     if occupancy is not None or (timing is None and not staged):
         # the single call: nerf_render_rays, or with a grid nerf_render_rays_occ (the grid's four arguments
         # go in front of the outputs)
@@ -131,7 +156,11 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
             inputs += [P(occupancy.bits.contiguous()), occupancy.resolution, occupancy.c_lo(), occupancy.c_inv()]
             entry, ws_bytes = "nerf_render_rays_occ", lib.nerf_render_occ_workspace_bytes
         ws = torch.empty(ws_bytes(B, N, Nf), dtype=torch.uint8, device=dev)
-        _lib.check(getattr(lib, entry)(*inputs, *outputs, P(ws), ws.numel(), _lib.stream()), entry)
+        tail = []
+        if bg_on:    # the _bg entries: the same arguments, then the background's in front of the stream
+            entry += "_bg"
+            tail = [P(bg), bg_rows, bd, P(acc), P(cacc)]
+        _lib.check(getattr(lib, entry)(*inputs, *outputs, P(ws), ws.numel(), *tail, _lib.stream()), entry)
         cw, cz = None, None
     else:
         cw, cz = _staged(lib, packed, o, d, B, near, far, N, Nf, t_vals, u_lin, perturb, tr, ur, seed or 0,
@@ -142,6 +171,10 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
         weights = weights[:, :0]
     extras["weights"] = weights.to(out)
     extras["z_vals"] = z_vals.to(out)
+    if bg_on:
+        extras["acc_map"] = acc.reshape(*orig_shape[:-1], 1).to(out)
+        if Nf:
+            extras["acc_map_coarse"] = cacc.reshape(*orig_shape[:-1], 1).to(out)
     if Nf:
         extras["rgb_map_coarse"] = crgb.reshape(*orig_shape[:-1], 3).to(out)
         extras["depth_map_coarse"] = cdepth.reshape(*orig_shape[:-1], 1).to(out)
@@ -149,6 +182,23 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
             extras["weights_coarse"] = cw.unsqueeze(-1).to(out)
             extras["z_vals_coarse"] = cz.to(out)
     return (rgb_map.reshape(*orig_shape[:-1], 3).to(out), depth_map.reshape(*orig_shape[:-1], 1).to(out), extras)
+
+
+def background_rows(background, B, dev):
+    """(bg, bg_rows) of a background= argument: None -> (None, 0); three floats -> a (1,3) tensor, 1; a
+    tensor of B x 3 values -> (B,3), B."""
+    if background is None:
+        return None, 0
+    if isinstance(background, torch.Tensor):
+        bg = background.detach().to(dev, torch.float32)
+    else:
+        bg = torch.tensor([float(v) for v in background], dtype=torch.float32, device=dev)
+    if bg.numel() == 3:
+        return bg.reshape(1, 3).contiguous(), 1
+    if bg.numel() != 3 * B:
+        raise ValueError(f"nerfmi.volume_render(background=): expected 3 floats or a ({B},3) tensor, got "
+                         f"{tuple(bg.shape)}")
+    return bg.reshape(B, 3).contiguous(), B
 
 
 def _staged(lib, packed, o, d, B, near, far, N, Nf, t_vals, u_lin, perturb, tr, ur, seed, ray0, app, rows, rgb_map,

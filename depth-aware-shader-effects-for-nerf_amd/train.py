@@ -22,7 +22,10 @@ and one image's rays form each batch (dataset.py:249-277).
 
 Not a reference feature: ``Trainer(hierarchical=True)`` / ``train_nerf(hierarchical=True)`` run the H1
 fine pass in every step and train on mse(fine) + coarse_loss_weight * mse(coarse)
-(nerf_train_hier_forward / nerf_train_hier_backward).
+(nerf_train_hier_forward / nerf_train_hier_backward).  Nor are ``background=`` and
+``acc_weight=``: the target is blended with a background colour through the dataset's alpha channel, the
+prediction is composited over the same colour, and the ray's opacity is pulled towards alpha (the _bg
+backwards of include/nerfmi_train.h).  The reference's ``background_color`` stays ignored.
 """
 import ctypes
 import math
@@ -64,12 +67,25 @@ class Trainer:
     and trains on loss = mse(fine) + ``coarse_loss_weight`` * mse(coarse) (include/nerfmi_train.h
     "training with the hierarchical fine pass").  forward_backward then returns that
     loss with the fine (merged) rgb_map and leaves the two device floats (fine, coarse) on
-    ``self.loss_parts``.  Not combined with ``occupancy``."""
+    ``self.loss_parts``.  Not combined with ``occupancy``.
+
+    ``background``: None (default: the step makes the calls it always made), three floats, or "random"
+    (one colour per ray from the library's counter RNG, keyed by the step's seed, which carries the rank).
+    A step then takes the batch's ``alpha`` (B,), None = ones, trains on
+    mse(rgb_map + k bg, alpha target + (1 - alpha) bg) + ``acc_weight`` * mse(acc, alpha) with acc the
+    ray's opacity and k = max(0, 1 - acc), returns the blended map, and leaves the parts on
+    ``self.loss_parts``: (colour, opacity), or with ``hierarchical`` (fine colour, coarse colour, fine
+    opacity, coarse opacity).  ``acc_weight`` > 0 works without a background too (black); a trainer with
+    neither refuses an ``alpha`` (ValueError), so ``loss_parts`` is allocated once, by configuration.  The
+    forwards are unchanged; it works dense, with ``occupancy`` and with
+    ``hierarchical``."""
 
     def __init__(self, config, model=None, appearance_embeddings=None, n_images=None, group=None,
                  lr=None, betas=(0.9, 0.999), eps=1e-8, near=None, far=None, occupancy=None,
-                 occupancy_refresh=None, hierarchical=False, n_importance=None, coarse_loss_weight=1.0):
+                 occupancy_refresh=None, hierarchical=False, n_importance=None, coarse_loss_weight=1.0,
+                 background=None, acc_weight=0.0):
         _check_occupancy_args(occupancy, occupancy_refresh)
+        self.background, self.acc_weight = _check_background_args(background, acc_weight)
         self.hierarchical, self.n_importance, self.coarse_loss_weight = _check_hierarchical_args(
             config, hierarchical, n_importance, coarse_loss_weight, occupancy)
         self.config = config
@@ -143,9 +159,15 @@ class Trainer:
         self._ws = None
         self._tvals = {}
         self._side = None          # side stream for the transposed packing (forward_backward)
+        self._bg_row = None        # the fixed background colour as a (1,3) device tensor
         if self.hierarchical:
-            self.loss_parts = torch.zeros(2, device=self.dev)   # (fine, coarse) mean squared errors
+            # (fine, coarse) mean squared errors; with a background (fine colour, coarse colour, fine
+            # opacity, coarse opacity)
+            self._loss4 = torch.zeros(4, device=self.dev)
+            self.loss_parts = self._loss4 if self._bg_configured() else self._loss4[:2]
             self._ws_hier = None
+        elif self._bg_configured():
+            self.loss_parts = torch.zeros(2, device=self.dev)   # (colour, opacity)
         self.occupancy = occupancy
         self.occupancy_refresh = None
         self.live_fraction = None  # share of the last step's samples the grid marked live
@@ -208,6 +230,35 @@ class Trainer:
                 self.app_grad.zero_()
         self._join.record(self._side)
 
+    def _bg_configured(self):
+        return self.background is not None or self.acc_weight > 0.0
+
+    def _bg_args(self, B, seed, alpha):
+        """None for a trainer without a background or an opacity term (the original calls; an alpha is
+        refused there); else the _bg backward's (alpha, bg, bg_rows, acc_weight, rgb_final)."""
+        if not self._bg_configured():
+            if alpha is not None:
+                raise ValueError("Trainer: alpha belongs to a trainer with background= or acc_weight > 0")
+            return None
+        if alpha is not None:
+            alpha = alpha.reshape(-1).to(self.dev, torch.float32).contiguous()
+            if alpha.shape[0] != B:
+                raise ValueError(f"Trainer: alpha has {alpha.shape[0]} values for {B} rays")
+        bg, rows = None, 0
+        if self.background == "random":
+            bg, rows = random_background(B, seed, self.dev), B
+        elif self.background is not None:
+            if self._bg_row is None:
+                self._bg_row = torch.tensor([self.background], dtype=torch.float32, device=self.dev)
+            bg, rows = self._bg_row, 1
+        return alpha, bg, rows, float(self.acc_weight), torch.empty(B, 3, device=self.dev)
+
+    def validation_background(self):
+        """The fixed colour a validation render composites over: the trainer's, white for "random"."""
+        if self.background is None:
+            return None
+        return (1.0, 1.0, 1.0) if self.background == "random" else self.background
+
     def _zero_unused_projection(self, rows):
         if rows == 0:   # appearance_projection unused: its gradient is zero, as torch leaves it (None → no update)
             self.view(self.grad, 20).zero_()
@@ -215,11 +266,13 @@ class Trainer:
 
     # ------------------------------------------------------------------------------ one step
     def forward_backward(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, u_rand=None, seed=None,
-                         _marks=None):
+                         alpha=None, _marks=None):
         """Loss (device scalar) and gradients in self.grad for one batch (train.py:77-90).
         rays (B,3) and target (B,3) on the device; app_idx: the batch's image (appearance row).
         t_rand (B,N) = the torch.rand draw of ray_utils.py:80; else the in-kernel RNG on `seed`.
-        u_rand (B,n_importance): the fine pass's draws (hierarchical trainers only)."""
+        u_rand (B,n_importance): the fine pass's draws (hierarchical trainers only).
+        alpha (B,): the target pixels' alpha channel (trainers with a background; None = ones); with a
+        background the returned map is the blended one."""
         lib, s, P = self.lib, _lib.stream(), _lib.ptr
         N = self.config.num_samples
         o, d, tgt = self._batch(rays_o, rays_d, target)
@@ -229,12 +282,13 @@ class Trainer:
             assert t_rand.shape == (B, N)
         if seed is None:
             seed = step_seed(self.steps + 1, self.rank)
+        bgo = self._bg_args(B, seed, alpha)
         if self.hierarchical:
-            return self._forward_backward_hier(o, d, tgt, app_idx, t_rand, u_rand, seed, _marks)
+            return self._forward_backward_hier(o, d, tgt, app_idx, t_rand, u_rand, seed, _marks, bgo)
         if u_rand is not None:
             raise ValueError("Trainer: u_rand belongs to the fine pass; construct the trainer with hierarchical=True")
         if self.occupancy is not None:
-            return self._forward_backward_occ(o, d, tgt, app_idx, t_rand, seed, _marks)
+            return self._forward_backward_occ(o, d, tgt, app_idx, t_rand, seed, _marks, bgo)
         _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
         main = torch.cuda.current_stream(self.dev)
         self._pack_transposed_aside(main)
@@ -251,13 +305,20 @@ class Trainer:
         # d app of the batch's image goes straight into its row of the table's gradient
         dapp = self.app_grad[int(app_idx)] if rows else None
         main.wait_event(self._join)
+        if bgo is not None:
+            al, bg, bg_rows, aw, final = bgo
+            _lib.check(lib.nerf_train_backward_bg(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, P(app),
+                                                  rows, self.grad_ptrs, P(dapp), P(self.loss_parts), P(ws), ws.numel(),
+                                                  P(al), P(bg), bg_rows, aw, P(final), s), "nerf_train_backward_bg")
+            self._zero_unused_projection(rows)
+            return self.loss_parts[0] + aw * self.loss_parts[1], final
         _lib.check(lib.nerf_train_backward(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, P(app), rows,
                                            self.grad_ptrs, P(dapp), P(self.loss_buf), P(ws), ws.numel(), s),
                    "nerf_train_backward")
         self._zero_unused_projection(rows)
         return self.loss_buf[0], rgb_map
 
-    def _forward_backward_hier(self, o, d, tgt, app_idx, t_rand, u_rand, seed, _marks=None):
+    def _forward_backward_hier(self, o, d, tgt, app_idx, t_rand, u_rand, seed, _marks=None, bgo=None):
         """forward_backward with the fine pass: nerf_train_hier_forward + nerf_train_hier_backward on one
         workspace that carries both sample sets' saves."""
         lib, s, P = self.lib, _lib.stream(), _lib.ptr
@@ -289,6 +350,15 @@ class Trainer:
             _marks[1].record(main)
         dapp = self.app_grad[int(app_idx)] if rows else None
         main.wait_event(self._join)
+        if bgo is not None:
+            al, bg, bg_rows, aw, final = bgo
+            _lib.check(lib.nerf_train_hier_backward_bg(P(self.packed), P(self.packedT), P(rgb_map), P(rgb_c), P(tgt), B,
+                                                       N, Nf, self.coarse_loss_weight, P(app), rows, self.grad_ptrs,
+                                                       P(dapp), P(self.loss_parts), P(ws), ws.numel(), P(al), P(bg),
+                                                       bg_rows, aw, P(final), None, s), "nerf_train_hier_backward_bg")
+            self._zero_unused_projection(rows)
+            lp, cw = self.loss_parts, self.coarse_loss_weight
+            return (lp[0] + aw * lp[2]) + cw * (lp[1] + aw * lp[3]), final
         _lib.check(lib.nerf_train_hier_backward(P(self.packed), P(self.packedT), P(rgb_map), P(rgb_c), P(tgt), B, N, Nf,
                                                 self.coarse_loss_weight, P(app), rows, self.grad_ptrs, P(dapp),
                                                 P(self.loss_parts), P(ws), ws.numel(), s), "nerf_train_hier_backward")
@@ -296,7 +366,7 @@ class Trainer:
         loss = self.loss_parts[0] + self.coarse_loss_weight * self.loss_parts[1]
         return loss, rgb_map
 
-    def _forward_backward_occ(self, o, d, tgt, app_idx, t_rand, seed, _marks=None):
+    def _forward_backward_occ(self, o, d, tgt, app_idx, t_rand, seed, _marks=None, bgo=None):
         """forward_backward on the live samples of self.occupancy: sample + classify, the live count
         to pinned host memory behind an event, the two weight packings (which cover that copy), the
         wait, then the gathered forward and the compact backward."""
@@ -334,6 +404,14 @@ class Trainer:
             _marks[1].record(main)
         dapp = self.app_grad[int(app_idx)] if rows else None
         main.wait_event(self._join)
+        if bgo is not None:
+            al, bg, bg_rows, aw, final = bgo
+            _lib.check(lib.nerf_train_occ_backward_bg(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, m_live,
+                                                      P(app), rows, self.grad_ptrs, P(dapp), P(self.loss_parts), P(ws),
+                                                      ws.numel(), P(al), P(bg), bg_rows, aw, P(final), s),
+                       "nerf_train_occ_backward_bg")
+            self._zero_unused_projection(rows)
+            return self.loss_parts[0] + aw * self.loss_parts[1], final
         _lib.check(lib.nerf_train_occ_backward(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, m_live,
                                                P(app), rows, self.grad_ptrs, P(dapp), P(self.loss_buf), P(ws),
                                                ws.numel(), s), "nerf_train_occ_backward")
@@ -419,8 +497,9 @@ class Trainer:
         if r is not None and self.steps >= r["warmup"] and (self.steps == r["warmup"] or self.steps % r["every"] == 0):
             self._rebuild_occupancy()
 
-    def step(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, u_rand=None, seed=None):
-        loss, rgb = self.forward_backward(rays_o, rays_d, target, app_idx, t_rand=t_rand, u_rand=u_rand, seed=seed)
+    def step(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, u_rand=None, seed=None, alpha=None):
+        loss, rgb = self.forward_backward(rays_o, rays_d, target, app_idx, t_rand=t_rand, u_rand=u_rand, seed=seed,
+                                          alpha=alpha)
         self.all_reduce()
         self.optimizer_step()
         return loss
@@ -514,6 +593,37 @@ def _check_hierarchical_args(config, hierarchical, n_importance, coarse_loss_wei
     return True, int(nf), cw
 
 
+def _check_background_args(background, acc_weight):
+    """(background, acc_weight) checked: None, "random" or a tuple of three finite floats, and a finite
+    float >= 0; ValueError otherwise (no device needed)."""
+    aw = float(acc_weight)
+    if not (aw >= 0.0 and math.isfinite(aw)):
+        raise ValueError(f"Trainer: acc_weight must be finite and >= 0, got {acc_weight!r}")
+    if background is None or (isinstance(background, str) and background == "random"):
+        return background, aw
+    try:
+        bg = tuple(float(v) for v in background)
+    except (TypeError, ValueError):
+        bg = ()
+    if isinstance(background, str) or len(bg) != 3 or not all(math.isfinite(v) for v in bg):
+        raise ValueError(f'Trainer: background must be None, "random" or three finite floats, got {background!r}')
+    return bg, aw
+
+
+_BACKGROUND_KEY = 0xBAC6C0105EED        # the random backgrounds' stream: the step's seed ^ this
+
+
+def random_background(B, seed, dev=None):
+    """(B,3) uniform colours of a step: value c of ray r is draw 3 r + c of the library's counter
+    generator (include/nerfmi.h, nerf_rng_uniforms) keyed by seed ^ _BACKGROUND_KEY, so the same
+    (step seed, rank) repeats them and different steps or ranks differ."""
+    dev = _lib.device() if dev is None else dev
+    out = torch.empty(B, 3, device=dev)
+    _lib.check(_lib.load().nerf_rng_uniforms((int(seed) ^ _BACKGROUND_KEY) & ((1 << 64) - 1), 0, 3 * B,
+                                             _lib.ptr(out), _lib.stream()), "nerf_rng_uniforms")
+    return out
+
+
 def step_seed(key, rank):
     """Key of a step's in-kernel jitter stream: distinct per step and per data-parallel rank (the
     reference draws torch.rand per call, ray_utils.py:80; ranks must not share draws)."""
@@ -546,7 +656,8 @@ def average_gradients(flat_grad, group):
 
 def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iterations=None, log_every=10,
                checkpoint_every=1000, seed=None, plots=True, return_metrics=False, occupancy=None,
-               occupancy_refresh=None, hierarchical=False, n_importance=None, coarse_loss_weight=1.0):
+               occupancy_refresh=None, hierarchical=False, n_importance=None, coarse_loss_weight=1.0,
+               background=None, acc_weight=0.0, trainer_cls=None):
     """src/train.py:13-207 on nerfmi: returns the trained model, as the reference does
     (train.py:207; run.py:347 assigns it).  ``return_metrics=True`` returns (model, losses, psnrs)
     instead; the per-iteration losses and PSNRs are also left on ``train_nerf.losses`` /
@@ -558,18 +669,27 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
     go to the Trainer (training on the live samples of an occupancy grid); the final and periodic
     checkpoints then carry the grid's state_dict under "occupancy".  ``hierarchical`` /
     ``n_importance`` / ``coarse_loss_weight`` go to the Trainer too (coarse + fine loss): the logged
-    loss and PSNR are then the fine pass's, and the validation render is hierarchical."""
+    loss and PSNR are then the fine pass's, and the validation render is hierarchical.  ``background`` /
+    ``acc_weight`` go to the Trainer as well: with a background or an opacity weight set every step gets the
+    batch's alpha channel (``batch["alpha"]``; None, the custom format, means ones), the logged loss and PSNR are the
+    colour term's, and the validation render composites over the trainer's colour (white for "random").
+    ``trainer_cls`` (tests): the class constructed instead of Trainer."""
     import torch.distributed as dist
     _check_occupancy_args(occupancy, occupancy_refresh)
+    _check_background_args(background, acc_weight)
     _check_hierarchical_args(config, hierarchical, n_importance, coarse_loss_weight, occupancy)
     rank = dist.get_rank(group) if group is not None else 0
     if rank == 0:
         os.makedirs(save_dir, exist_ok=True)
     initial_batch_size = min(64, config.batch_size)                    # train.py:26
-    trainer = Trainer(config, appearance_embeddings=getattr(dataset, "appearance_embeddings", None),
-                      n_images=len(dataset), group=group, near=getattr(dataset, "near", None),
-                      far=getattr(dataset, "far", None), occupancy=occupancy, occupancy_refresh=occupancy_refresh,
-                      hierarchical=hierarchical, n_importance=n_importance, coarse_loss_weight=coarse_loss_weight)
+    bg_kwargs = {}
+    if background is not None or float(acc_weight) != 0.0:
+        bg_kwargs = dict(background=background, acc_weight=acc_weight)
+    trainer = (trainer_cls or Trainer)(
+        config, appearance_embeddings=getattr(dataset, "appearance_embeddings", None), n_images=len(dataset),
+        group=group, near=getattr(dataset, "near", None), far=getattr(dataset, "far", None), occupancy=occupancy,
+        occupancy_refresh=occupancy_refresh, hierarchical=hierarchical, n_importance=n_importance,
+        coarse_loss_weight=coarse_loss_weight, **bg_kwargs)
     iters = config.num_iterations if num_iterations is None else num_iterations
     losses, psnrs = [], []
     train_nerf.losses, train_nerf.psnrs = losses, psnrs
@@ -578,11 +698,14 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
     for i in range(1, iters + 1):
         batch = dataset.get_rays(batch_size=initial_batch_size) if i <= 5 else dataset.get_rays()
         app_idx = batch["appearance_idx"] if config.use_appearance else None
+        step_kwargs = {"alpha": batch.get("alpha")} if bg_kwargs else {}
         loss = trainer.step(batch["rays_o"], batch["rays_d"], batch["rgb"], app_idx,
-                            seed=None if seed is None else step_seed(seed * 1_000_003 + i, trainer.rank))
+                            seed=None if seed is None else step_seed(seed * 1_000_003 + i, trainer.rank),
+                            **step_kwargs)
         if i % config.scheduler_step_size == 0:                          # StepLR, train.py:95-96
             trainer.lr *= config.scheduler_gamma
-        loss_v = float(trainer.loss_parts[0]) if trainer.hierarchical else float(loss)   # the fine MSE
+        # the fine MSE; with a background or an opacity term the (fine) colour term
+        loss_v = float(trainer.loss_parts[0]) if (trainer.hierarchical or bg_kwargs) else float(loss)
         psnr_v = -10.0 * math.log10(loss_v) if loss_v > 0 else float("inf")
         losses.append(loss_v)
         psnrs.append(psnr_v)
@@ -592,7 +715,8 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
             torch.save(trainer.checkpoint(loss_v, psnr_v, i), os.path.join(save_dir, f"checkpoint_{i:06d}.pt"))
             if plots:
                 validation_render(trainer.model, dataset, config, i, save_dir, hierarchical=trainer.hierarchical,
-                                  n_importance=trainer.n_importance)
+                                  n_importance=trainer.n_importance,
+                                  **({"background": trainer.validation_background()} if background is not None else {}))
     if rank == 0:
         torch.save(trainer.checkpoint(loss_v, psnr_v, iters), os.path.join(save_dir, "checkpoint_final.pt"))
         if plots:
@@ -604,11 +728,12 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
 
 
 @torch.no_grad()
-def validation_render(model, dataset, config, iteration, save_dir, hierarchical=False, n_importance=None):
+def validation_render(model, dataset, config, iteration, save_dir, hierarchical=False, n_importance=None,
+                      background=None):
     """The sample render of train.py:127-173: the first 1000 rays of the last image, coarse
     volume_render with perturb=False (``hierarchical``: the H1 fine pass with n_importance samples, as
-    a hierarchical trainer trained it), RGB and viridis depth side by side in
-    render_{iteration:06d}.png.  Returns (rgb (1000,3), depth (1000,1))."""
+    a hierarchical trainer trained it; ``background``: three floats the render is composited over), RGB
+    and viridis depth side by side in render_{iteration:06d}.png.  Returns (rgb (1000,3), depth (1000,1))."""
     from .render import volume_render
     val = dataset.get_rays(idx=len(dataset) - 1)
     o, d = val["rays_o"][:1000], val["rays_d"][:1000]
@@ -617,7 +742,8 @@ def validation_render(model, dataset, config, iteration, save_dir, hierarchical=
         app = dataset.appearance_embeddings[val["appearance_idx"]]
     rgb, depth, _ = volume_render(model, o, d, near=dataset.near, far=dataset.far, n_samples=config.num_samples,
                                   n_importance=config.num_importance if n_importance is None else n_importance,
-                                  appearance_embedding=app, perturb=False, hierarchical=hierarchical)
+                                  appearance_embedding=app, perturb=False, hierarchical=hierarchical,
+                                  **({} if background is None else {"background": background}))
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt

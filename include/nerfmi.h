@@ -255,6 +255,42 @@ int nerf_render_rays_occ(const float* packed, const float* rays_o, const float* 
                          float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
                          nerf_stream_t stream);
 
+/* ------------------------------------------- opacity map and background
+ * Not a reference feature (its background_color is accepted and ignored, and stays so); additions to
+ * ABI 11, nothing above changes.  Definitions, per ray r:
+ *   acc[r]   = (float) sum w, the composite's own double sum of its weights, rounded once
+ *   k[r]     = max(0.0f, 1.0f - acc[r])
+ *   rgb_map  = rgb_map + k * bg   per channel, the product rounded, then the sum (no FMA)
+ *   depth    = (float) sum w z + k * bd: the expected depth with the background at depth bd
+ * bg: (bg_rows, 3) floats, bg_rows 0 (no blend; bg may be null), 1 (one colour) or B (one per ray).
+ * bd: NaN keeps the normalised depth sum w z / (sum w + 1e-10) of the entries above.  acc_map (B) and
+ * coarse_acc (B; written only when Nf > 0) are nullable.  An empty ray (every sigma 0, or every sample
+ * dead under a grid) has acc == 0, colour == bg and depth == bd, bit for bit; a ray with acc >= 1 keeps
+ * rgb_map's bits.  The coarse maps of the render entries get the same blend.  With every option off
+ * (bg_rows 0, bd NaN, no opacity output) each entry makes the launches of its original and returns
+ * its bits; bg_rows outside {0, 1, B} or a null bg with bg_rows > 0 is NERF_ERR_BAD_ARG.  Workspaces,
+ * chunking and every other error are the originals'. */
+int nerf_composite_bg(const float* rgb, const float* sigma, const float* z_vals, int64_t B, int N,
+                      float* rgb_map, float* depth_map, float* weights, const float* bg,
+                      int64_t bg_rows, float bd, float* acc_map, nerf_stream_t stream);
+int nerf_render_rays_bg(const float* packed, const float* rays_o, const float* rays_d, int64_t B,
+                        double near, double far, int N, int Nf, const float* t_vals,
+                        const float* u_lin, int perturb, const float* t_rand, const float* u_rand,
+                        uint64_t seed, int64_t ray0, const float* app, int64_t app_rows,
+                        float* rgb_map, float* depth_map, float* weights_out, float* z_out,
+                        float* coarse_rgb, float* coarse_depth, void* workspace, size_t ws_bytes,
+                        const float* bg, int64_t bg_rows, float bd, float* acc_map,
+                        float* coarse_acc, nerf_stream_t stream);
+int nerf_render_rays_occ_bg(const float* packed, const float* rays_o, const float* rays_d, int64_t B,
+                            double near, double far, int N, int Nf, const float* t_vals,
+                            const float* u_lin, int perturb, const float* t_rand,
+                            const float* u_rand, uint64_t seed, int64_t ray0, const float* app,
+                            int64_t app_rows, const uint32_t* bits, int G, const float* lo,
+                            const float* inv, float* rgb_map, float* depth_map, float* weights_out,
+                            float* z_out, float* coarse_rgb, float* coarse_depth, void* workspace,
+                            size_t ws_bytes, const float* bg, int64_t bg_rows, float bd,
+                            float* acc_map, float* coarse_acc, nerf_stream_t stream);
+
 /* ------------------------------------------------- depth-aware post effects
  * The depth-reading effects of the reference's PostProcessor (src/post_processor.py) on the
  * frame run.py renders.  image / out: uint8 (H,W,3) RGB; depth: fp32 (H,W)

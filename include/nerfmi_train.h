@@ -137,7 +137,65 @@ int nerf_train_hier_backward(const float* packed, const float* packedT, const fl
                              float* const* param_grads, float* dapp, float* loss /* 2 floats */,
                              void* workspace, size_t ws_bytes, nerf_stream_t stream);
 
+/* ------------------------------------------------------- training with a background
+ * The three backwards above with the dataset's alpha channel, a background colour and an opacity
+ * term (not reference features; additions to ABI 11).  THE FORWARDS ARE UNCHANGED: a
+ * _bg backward follows the same forward on the same workspace, takes the rgb_map (and coarse_rgb)
+ * that forward returned, and recomputes each ray's opacity acc = (float) sum w (nerfmi.h, "opacity
+ * map and background") from the rgb / sigma / z rows the forward left in the workspace: the dense
+ * rows, under a grid the dense zero-filled rows, and for the fine pass the merged rows through
+ * merged_src.  Per ray, with k = max(0, 1 - acc) and each product and sum rounded on its own:
+ *   target' = alpha * target + (1 - alpha) * bg        alpha (B) nullable = 1
+ *   final   = rgb_map + k * bg                         bg (bg_rows,3), bg_rows 0 (black), 1 or B
+ *   colour loss  = mean over B x 3 of (final - target')^2
+ *   opacity loss = mean over B of (acc - alpha)^2
+ *   total   = colour + acc_weight * opacity            acc_weight >= 0
+ * so d total / d rgb_map = 2 (final - target') / (3B) and d total / d acc = -(bg . that) where k > 0
+ * (else 0) + acc_weight * 2 (acc - alpha) / B, which reaches every weight of the ray.  loss receives
+ * the parts: dense and grid loss[0] colour, loss[1] opacity; hierarchical four floats, fine colour,
+ * coarse colour, fine opacity, coarse opacity, total = fine + coarse_weight * coarse with each part
+ * colour + acc_weight * opacity.  rgb_final (B,3) (and coarse_final) nullable: the blended colour.
+ * Deterministic (fixed-order reductions, no float atomics).  The scratch lies in the workspace's
+ * gradient rows: the workspace sizes above hold.  With every option off (alpha null, bg_rows 0,
+ * acc_weight 0) an entry makes its original's calls and returns its bits; the opacity parts then read
+ * 0 and rgb_final is rgb_map.  bg_rows outside {0, 1, B}, a null bg with bg_rows > 0 and an acc_weight
+ * that is negative or NaN are NERF_ERR_BAD_ARG; every other refusal is the original's. */
+int nerf_train_backward_bg(const float* packed, const float* packedT, const float* rgb_map,
+                           const float* target, int64_t B, int N, const float* app, int64_t app_rows,
+                           float* const* param_grads, float* dapp, float* loss /* 2 floats */,
+                           void* workspace, size_t ws_bytes, const float* alpha, const float* bg,
+                           int64_t bg_rows, double acc_weight, float* rgb_final, nerf_stream_t stream);
+int nerf_train_occ_backward_bg(const float* packed, const float* packedT, const float* rgb_map,
+                               const float* target, int64_t B, int N, int64_t M_live, const float* app,
+                               int64_t app_rows, float* const* param_grads, float* dapp,
+                               float* loss /* 2 floats */, void* workspace, size_t ws_bytes,
+                               const float* alpha, const float* bg, int64_t bg_rows, double acc_weight,
+                               float* rgb_final, nerf_stream_t stream);
+int nerf_train_hier_backward_bg(const float* packed, const float* packedT, const float* rgb_map,
+                                const float* coarse_rgb, const float* target, int64_t B, int N, int Nf,
+                                double coarse_weight, const float* app, int64_t app_rows,
+                                float* const* param_grads, float* dapp, float* loss /* 4 floats */,
+                                void* workspace, size_t ws_bytes, const float* alpha, const float* bg,
+                                int64_t bg_rows, double acc_weight, float* rgb_final,
+                                float* coarse_final, nerf_stream_t stream);
+
 /* -------------------------------------------------------------------- stages */
+/* nerf_composite_backward_grad and nerf_composite_merged_backward with g_acc (B, nullable = 0), the
+ * upstream gradient of the ray's opacity acc = sum w (added to every d w of the ray), and bd, the
+ * background depth the forward ran with: NaN = the normalised depth, else depth = sum w z + k bd and
+ * its term is grad_depth (z_s - bd) where k > 0, grad_depth z_s where k == 0.  The same arithmetic
+ * order (double scans, d sigma rounded once); with g_acc null or zero and bd NaN the same bits. */
+int nerf_composite_backward_grad_acc(const float* rgb, const float* sigma, const float* z_vals,
+                                     const float* grad_rgb_map, const float* grad_depth_map,
+                                     int64_t B, int N, float* dsigma, float* drgb, const float* g_acc,
+                                     float bd, nerf_stream_t stream);
+int nerf_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                                       const float* sigma_f, const uint16_t* merged_src,
+                                       const float* z_all, const float* grad_rgb_map,
+                                       const float* grad_depth_map, int64_t B, int N, int Nf,
+                                       int accumulate_coarse, float* dsigma_c, float* drgb_c,
+                                       float* dsigma_f, float* drgb_f, const float* g_acc, float bd,
+                                       nerf_stream_t stream);
 /* nerf_sample_importance that emits, beside z_all (B,N+Nf), the fine samples alone in sample order
  * (z_fine (B,Nf)) and for each merged slot which sample sits there: merged_src (B,N+Nf) uint16, an
  * index into cat[coarse (N), fine (Nf)].  The form nerf_render_rays uses internally. */

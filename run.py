@@ -85,10 +85,42 @@ def parse_args(argv=None):
     p.add_argument('--iterations', type=int, default=None, help='training iterations (default Config)')
     p.add_argument('--save_dir', type=str, default='checkpoints',
                    help="training checkpoint directory (the reference's train_nerf default, train.py:13)")
+    p.add_argument('--background', type=str, nargs='+', default=None, metavar='R G B | random',
+                   help='composite over this colour (three floats); "random": one colour per ray and step, train only')
+    p.add_argument('--background_depth', type=str, default=None, metavar='far|VALUE',
+                   help="depth of the background: an empty ray's depth is this instead of 0 (render modes only)")
+    p.add_argument('--acc_weight', type=float, default=0.0, metavar='W',
+                   help='weight of the opacity loss mse(acc, alpha) (train mode)')
+    p.add_argument('--save_acc', action='store_true', help='write the opacity map acc_*.png beside the depth (render modes only)')
     args = p.parse_args(argv)
     if args.mode == 'train' and args.hierarchical and args.occupancy:
         p.error("--hierarchical and --occupancy are not combined in --mode train (the hierarchical step runs on "
                 "every sample)")
+    if args.background is not None:
+        if args.background == ['random']:
+            if args.mode != 'train':
+                p.error("--background random is for --mode train (a render composites over one fixed colour)")
+            args.background = 'random'
+        else:
+            try:
+                args.background = tuple(float(v) for v in args.background)
+            except ValueError:
+                args.background = ()
+            if len(args.background) != 3 or not all(np.isfinite(args.background)):
+                p.error("--background takes three floats R G B, or the word random")
+    if args.background_depth is not None and args.background_depth != 'far':
+        try:
+            args.background_depth = float(args.background_depth)
+        except ValueError:
+            p.error("--background_depth takes the word far or a number")
+        if not np.isfinite(args.background_depth):
+            p.error("--background_depth takes the word far or a finite number")
+    if not (args.acc_weight >= 0.0 and np.isfinite(args.acc_weight)):
+        p.error("--acc_weight must be finite and >= 0")
+    if args.mode == 'train' and (args.background_depth is not None or args.save_acc):
+        p.error("--background_depth and --save_acc belong to the render modes (training writes no depth or opacity map)")
+    if args.mode != 'train' and args.acc_weight:
+        p.error("--acc_weight is for --mode train")
     return args
 
 
@@ -122,8 +154,10 @@ class SceneInfo:
 def render_path(model, scene, config, output_dir, num_frames=120, quality='high', width=800, height=800,
                 start_frame=0, end_frame=None, save_depth=False, raw_output=False, camera_path='circle',
                 spiral_loops=2.0, height_range=(-0.5, 0.5), hierarchical=False, n_importance=None, chunk=0,
-                seed=0, shader=None, occupancy=None):
-    """run.py:63-282 (render mode) on nerfmi."""
+                seed=0, shader=None, occupancy=None, background=None, background_depth=None, save_acc=False):
+    """run.py:63-282 (render mode) on nerfmi.  background (three floats), background_depth ('far' = the
+    scene's far plane, or a value) and save_acc are nerfmi's: with a background depth the
+    depth-aware effects read a depth that puts empty rays at that depth instead of 0."""
     import torch.distributed as dist
     from nerfmi import cameras, frames
     from nerfmi.render import render_rays
@@ -150,22 +184,33 @@ def render_path(model, scene, config, output_dir, num_frames=120, quality='high'
         kw = dict(appearance_embedding=app, perturb=perturb, hierarchical=hierarchical)
         if occupancy is not None:
             kw["occupancy"] = occupancy
+        if background is not None:
+            kw["background"] = background
+        if background_depth is not None:
+            kw["background_depth"] = float(scene.far) if background_depth == 'far' else float(background_depth)
+        if save_acc:
+            kw["return_acc"] = True
+        acc = None
         if world > 1 or not chunk:
-            rgb, depth = frames.render_path_frames(model, [c2w], height, width, focal, scene.near, scene.far,
-                                                   n_samples, n_imp, seed=seed + frame_idx, **kw)
-            rgb, depth = rgb[0], depth[0]
+            rgb, depth, *acc = frames.render_path_frames(model, [c2w], height, width, focal, scene.near, scene.far,
+                                                         n_samples, n_imp, seed=seed + frame_idx, **kw)
+            rgb, depth, acc = rgb[0], depth[0], (acc[0][0] if acc else None)
         else:
             from nerfmi import get_rays
             o, d = get_rays(height, width, focal, c2w.cuda())
             o, d = o.reshape(-1, 3), d.reshape(-1, 3)
             outs = [render_rays(model, o[j:j + chunk], d[j:j + chunk], scene.near, scene.far, n_samples, n_imp,
-                                seed=seed + frame_idx, ray_offset=j, **kw)[:2]
+                                seed=seed + frame_idx, ray_offset=j, **kw)
                     for j in range(0, o.shape[0], chunk)]
-            rgb = torch.cat([r for r, _ in outs]).reshape(height, width, 3)
-            depth = torch.cat([dd for _, dd in outs]).reshape(height, width)
+            rgb = torch.cat([r for r, _, _ in outs]).reshape(height, width, 3)
+            depth = torch.cat([dd for _, dd, _ in outs]).reshape(height, width)
+            if save_acc:
+                acc = torch.cat([ex["acc_map"] for _, _, ex in outs]).reshape(height, width)
         if rank != 0:
             continue
         write_frame(output_dir, frame_idx, rgb, depth, save_depth, raw_output, shader)
+        if acc is not None:
+            write_acc(output_dir, frame_idx, acc)
     if rank == 0:
         print(f"Rendered {len(theta)} frames to {output_dir}")
 
@@ -206,6 +251,14 @@ def write_frame(output_dir, frame_idx, rgb, depth, save_depth=False, raw_output=
     plt.axis('off')
     plt.savefig(os.path.join(output_dir, f'depth_{frame_idx:03d}.png'), bbox_inches='tight', pad_inches=0)
     plt.close()
+
+
+def write_acc(output_dir, frame_idx, acc):
+    """acc_{i:03d}.png beside the depth: the opacity map (H,W) in [0, 1] as 8-bit grey, by truncation
+    like the rgb image."""
+    from PIL import Image
+    img = (acc.clamp(0.0, 1.0) * 255).cpu().numpy().astype(np.uint8)
+    Image.fromarray(img, mode='L').save(os.path.join(output_dir, f'acc_{frame_idx:03d}.png'))
 
 
 def model_dimension_check(config):
@@ -264,8 +317,13 @@ def main(argv=None):
             if rank == 0:
                 n_imp = config.num_importance if args.n_importance is None else args.n_importance
                 print(f"Training hierarchically: {config.num_samples} coarse + {n_imp} fine samples per ray")
+        bg_kw = {}
+        if args.background is not None or args.acc_weight:   # blend through alpha (train.py, Trainer(background=))
+            bg_kw = dict(background=args.background, acc_weight=args.acc_weight)
+            if rank == 0:
+                print(f"Training over background {args.background}, opacity loss weight {args.acc_weight:g}")
         model = train_nerf(config, dataset, save_dir=args.save_dir, num_iterations=args.iterations,   # run.py:347
-                           group=group, **occ_kw, **hier_kw)
+                           group=group, **occ_kw, **hier_kw, **bg_kw)
         if group is not None:
             dist.destroy_process_group()
         return 0
@@ -302,7 +360,9 @@ def main(argv=None):
                     save_depth=args.save_depth, raw_output=args.raw_output, camera_path=args.camera_path,
                     spiral_loops=args.spiral_loops, height_range=args.height_range,
                     hierarchical=args.hierarchical, n_importance=args.n_importance, chunk=args.chunk,
-                    seed=args.seed, shader=shader, occupancy=occupancy)
+                    seed=args.seed, shader=shader, occupancy=occupancy,
+                    **{k: v for k, v in (("background", args.background), ("background_depth", args.background_depth))
+                       if v is not None}, **({"save_acc": True} if args.save_acc else {}))
     if group is not None:
         dist.destroy_process_group()
     return 0
