@@ -1,6 +1,7 @@
 """Seeded inputs of the trained-scene regime, and the gradient truth of the composite there — TEST
 INFRASTRUCTURE ONLY (tests/test_degenerate_cases_cpu.py shows on the CPU that each generator reaches
-the regime it names; tests/test_gpu_degenerate_rays.py feeds them to the kernels).
+the regime it names; tests/test_gpu_degenerate_rays.py and tests/test_gpu_degenerate_train.py feed them
+to the kernels).
 
 The regime: surfaces with sigma * dist of 20 and above (alpha == 1 in fp32, every later factor of the
 transmittance exactly 1e-10f, the product through float denormals to 0 within five samples), empty
@@ -109,6 +110,64 @@ def composite_f64_st(rgb, sigma, z, exp32=torch.exp):
     rgb_map = torch.sum(weights * rgb, dim=1)
     depth_map = torch.sum(weights * z32.double().unsqueeze(-1), dim=1) / (torch.sum(weights, dim=1) + 1e-10)
     return rgb_map, depth_map, weights
+
+
+def _dist32(z):
+    z32 = z.float()
+    return torch.cat([z32[..., 1:] - z32[..., :-1], torch.ones_like(z32[..., :1]) * 1e-3], dim=-1)
+
+
+def acc32_of(sigma, z, exp32=torch.exp):
+    """(B,) opacity as the kernels round it (composite_body.h, composite_bwd_body.h): the fp32 weights
+    alpha32 * (float) T, T the double product of the fp32 factors, summed in double and rounded once.
+    sigma is (B,N) or (B,N,1)."""
+    s32 = sigma.detach().float().reshape(z.shape)
+    a32 = 1.0 - exp32(-s32 * _dist32(z))
+    f32 = 1.0 - a32 + 1e-10
+    assert a32.dtype == f32.dtype == torch.float32
+    T = torch.cumprod(torch.cat([torch.ones_like(f32[:, :1]).double(), f32.double()], dim=1), dim=1)[:, :-1]
+    return (a32 * T.float()).double().sum(-1).float()
+
+
+def composite_f64_st_bg(rgb, sigma, z, bg=None, bd=None, exp32=torch.exp, gate=None):
+    """composite_f64_st with the opacity and the background blend: the same
+    straight-through composite (fp32 values of alpha and of 1 - alpha + 1e-10, float64 gradients), and
+      acc    = sum w                          (B,1)
+      colour = rgb_map + k bg                 (B,3)  bg (B,3) or (1,3), None: black
+      depth  = sum w z + k bd                 (B,1)  where bd is given, else the normalised depth
+    with k = gate (1 - acc) and gate = [acc32 < 1] a CONSTANT from acc32_of: the kernels' rule is k > 0,
+    strict (a saturated ray passes no gradient through k), where torch.clamp's backward passes the
+    gradient at exactly 1 - acc == 0.  `gate` (B,) bool overrides the rule (to measure what it changes).
+    Returns (rgb_map, depth, weights, acc, colour)."""
+    rgb_map, depth_map, weights = composite_f64_st(rgb, sigma, z, exp32)
+    acc = torch.sum(weights, dim=1)
+    if gate is None:
+        gate = acc32_of(sigma, z, exp32) < 1
+    k = gate.to(acc.dtype)[:, None] * (1.0 - acc)
+    colour = rgb_map if bg is None else rgb_map + k * bg.to(acc.dtype)
+    if bd is not None:
+        depth_map = torch.sum(weights * z.float().double().unsqueeze(-1), dim=1) + k * bd
+    return rgb_map, depth_map, weights, acc, colour
+
+
+def composite_f32_bg(rgb, sigma, z, bg=None, bd=None, gate=None):
+    """The fp32 baseline of composite_f64_st_bg: the oracle's composite (render.py:56-80) with the same
+    definitions in fp32 torch, under autograd.  The gate is acc32_of's as well (at torch's exp): torch's
+    own float-order sum of the weights lands on the other side of 1 on a few saturated rays."""
+    z32 = z.float()
+    alpha = 1.0 - torch.exp(-sigma * _dist32(z).unsqueeze(-1))
+    trans = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1, :]), 1.0 - alpha + 1e-10], dim=1), dim=1)[:, :-1, :]
+    weights = alpha * trans
+    rgb_map = torch.sum(weights * rgb, dim=1)
+    acc = torch.sum(weights, dim=1)
+    if gate is None:
+        gate = acc32_of(sigma, z) < 1
+    k = gate.to(acc.dtype)[:, None] * (1.0 - acc)
+    colour = rgb_map if bg is None else rgb_map + k * bg
+    swz = torch.sum(weights * z32.unsqueeze(-1), dim=1)
+    depth_map = swz / (acc + 1e-10) if bd is None else swz + k * bd
+    assert colour.dtype == depth_map.dtype == torch.float32
+    return rgb_map, depth_map, weights, acc, colour
 
 
 def peaked_weights(B, N, gen):
