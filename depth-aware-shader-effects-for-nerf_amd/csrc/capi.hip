@@ -470,7 +470,8 @@ int nerf_composite(const float* rgb, const float* sigma, const float* z_vals, in
   REQUIRE(B >= 0, "nerf_composite: B=%lld", (long long)B);
   if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite: N=%d (1..4096)", N);
   REQUIRE(B == 0 || (rgb && sigma && z_vals && rgb_map && depth_map), "nerf_composite: null pointer");
-  return launch_composite(rgb, sigma, z_vals, B, N, rgb_map, depth_map, weights, (hipStream_t)stream);
+  return launch_composite(dense_samples(rgb, sigma, z_vals, B, N), rgb_map, depth_map, weights, nullptr,
+                          (hipStream_t)stream);
 }
 
 // The background arguments of the _bg entries: bg_rows in {0, 1, B}, bg non-null when bg_rows > 0.
@@ -488,10 +489,10 @@ int nerf_composite_bg(const float* rgb, const float* sigma, const float* z_vals,
   if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_bg: N=%d (1..4096)", N);
   if (int rc = check_bg("nerf_composite_bg", bg, bg_rows, B)) return rc;
   REQUIRE(B == 0 || (rgb && sigma && z_vals && rgb_map && depth_map), "nerf_composite_bg: null pointer");
-  if (bg_rows == 0 && bd != bd && !acc_map)   // every option off: nerf_composite's launch
-    return launch_composite(rgb, sigma, z_vals, B, N, rgb_map, depth_map, weights, (hipStream_t)stream);
+  const bool off = bg_rows == 0 && bd != bd && !acc_map;   // every option off: nerf_composite's launch
   const CompositeBg bga{bg_rows ? bg : nullptr, bg_rows > 1 ? 3 : 0, bd, acc_map};
-  return launch_composite_bg(rgb, sigma, z_vals, B, N, rgb_map, depth_map, weights, bga, (hipStream_t)stream);
+  return launch_composite(dense_samples(rgb, sigma, z_vals, B, N), rgb_map, depth_map, weights, off ? nullptr : &bga,
+                          (hipStream_t)stream);
 }
 
 // --------------------------------------------------------------- occupancy-grid sample skipping
@@ -678,13 +679,15 @@ static int render_chunk(const RenderArgs& a, const OccGrid* grid, const RenderBg
     if ((rc = profiled(s, B * (int64_t)n, dense))) return rc;
     return classify();
   };
-  // the two composites: today's launches, or with a background / opacity request the _bg kernels (the
-  // coarse maps get the same blend)
-  auto composite = [&](float* rgb_map, float* depth, float* wts, float* acc) -> int {
-    if (!bgo) return launch_composite(w.rgb_c, w.sigma_c, z, B, N, rgb_map, depth, wts, s);
-    const CompositeBg bga{bgo->bg_rows ? bgo->bg : nullptr, bgo->bg_rows > 1 ? 3 : 0, bgo->bd, acc};
-    return launch_composite_bg(w.rgb_c, w.sigma_c, z, B, N, rgb_map, depth, wts, bga, s);
+  // the two composites: the plain launches, or with a background / opacity request the _bg kernels (the
+  // coarse maps get the same blend, each composite its own opacity map)
+  CompositeBg bga{};
+  if (bgo) bga = {bgo->bg_rows ? bgo->bg : nullptr, bgo->bg_rows > 1 ? 3 : 0, bgo->bd, nullptr};
+  auto composite = [&](const CompositeSamples& in, float* rgb_map, float* depth, float* wts, float* acc) -> int {
+    bga.acc_map = acc;
+    return launch_composite(in, rgb_map, depth, wts, bgo ? &bga : nullptr, s);
   };
+  const CompositeSamples coarse = dense_samples(w.rgb_c, w.sigma_c, z, B, N);
   int rc;
   // render.py:19's normalisation in the ray-feature kernel (it writes dn)
   if ((rc = launch_ray_features(a.packed, a.rays_d, B, a.app, a.app_rows, w.feat, s, nullptr, dn))) return rc;
@@ -692,10 +695,10 @@ static int render_chunk(const RenderArgs& a, const OccGrid* grid, const RenderBg
                               a.t_rand, seed_c, z, nullptr, s)))
     return rc;                                                                                 // render.py:22
   if ((rc = mlp(z, N, w.rgb_c, w.sigma_c))) return rc;                                         // :49
-  if (Nf == 0) return composite(a.rgb_map, a.depth_map, wc, bgo ? bgo->acc_map : nullptr);     // render.py:56-80
+  if (Nf == 0) return composite(coarse, a.rgb_map, a.depth_map, wc, bgo ? bgo->acc_map : nullptr);   // render.py:56-80
   float* crgb = a.coarse_rgb ? a.coarse_rgb : w.maps;
   float* cdepth = a.coarse_depth ? a.coarse_depth : w.maps + 3 * B;
-  if ((rc = composite(crgb, cdepth, wc, bgo ? bgo->coarse_acc : nullptr))) return rc;
+  if ((rc = composite(coarse, crgb, cdepth, wc, bgo ? bgo->coarse_acc : nullptr))) return rc;
   // H1 fine pass: resample + merge (each merged slot records which coarse or fine sample it holds),
   // the MLP run on the Nf new samples only, in sample order, and the composite over all N+Nf merged
   // samples gathering the coarse evaluations and the fine ones through the map.  (Round 3 scattered
@@ -705,13 +708,8 @@ static int render_chunk(const RenderArgs& a, const OccGrid* grid, const RenderBg
                               nullptr, nullptr, nullptr, w.z_fine, nullptr, s, w.merged_src)))
     return rc;
   if ((rc = mlp(w.z_fine, Nf, w.rgb_f, w.sigma_f))) return rc;
-  if (bgo) {
-    const CompositeBg bga{bgo->bg_rows ? bgo->bg : nullptr, bgo->bg_rows > 1 ? 3 : 0, bgo->bd, bgo->acc_map};
-    return launch_composite_merged_bg(w.rgb_c, w.sigma_c, w.rgb_f, w.sigma_f, w.merged_src, z_all, B, N, Nf, a.rgb_map,
-                                      a.depth_map, a.weights_out, bga, s);
-  }
-  return launch_composite_merged(w.rgb_c, w.sigma_c, w.rgb_f, w.sigma_f, w.merged_src, z_all, B, N, Nf, a.rgb_map,
-                                 a.depth_map, a.weights_out, s);
+  return composite(merged_samples(w.rgb_c, w.sigma_c, w.rgb_f, w.sigma_f, w.merged_src, z_all, B, N, Nf), a.rgb_map,
+                   a.depth_map, a.weights_out, bgo ? bgo->acc_map : nullptr);
 }
 
 // Both entry points: the checks, then the chunk loop.  Calls past the launch-size limit run in ray

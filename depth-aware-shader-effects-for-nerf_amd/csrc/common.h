@@ -182,26 +182,37 @@ int launch_occ_dilate(const uint32_t* in, int G, uint32_t* out, hipStream_t s);
 int launch_mlp(const float* packed, const float* o, const float* d, const float* z, int64_t R,
                int N, const float* feat, float* rgb, float* sigma, const int* out_slot, int out_T,
                hipStream_t s, float* save = nullptr, const float* encd = nullptr, uint32_t* masks = nullptr);
-int launch_composite(const float* rgb, const float* sigma, const float* z, int64_t B, int N,
-                     float* rgb_map, float* depth, float* weights, hipStream_t s);
-// The fine composite of nerf_render_rays: merged slot p of ray r holds sample src[r T + p] of
-// cat[coarse (rgb_c, sigma_c: N per ray), fine (rgb_f, sigma_f: Nf per ray)], z_all its z.
-int launch_composite_merged(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
-                            const uint16_t* src, const float* z_all, int64_t B, int N, int Nf, float* rgb_map,
-                            float* depth, float* weights, hipStream_t s);
-// The composites with the opacity output and the background blend (composite.hip):
-// bg null = no blend, else bg + stride * r is ray r's colour (stride 0: one colour, 3: one per ray);
-// bd NaN = the normalised depth, else the depth of the background; acc_map (B) nullable.
+// The samples a composite runs over, B rays (composite.hip, composite_bwd.hip): dense, N per ray in
+// (rgb, sigma, z), or merged (the fine composite of nerf_render_rays and the hierarchical step): slot p
+// of ray r holds sample src[r T + p] of cat[coarse (rgb, sigma: N per ray), fine (rgb_f, sigma_f: Nf
+// per ray)], T = N + Nf, and z is the merged row z_all.
+struct CompositeSamples {
+  const float *rgb, *sigma, *rgb_f, *sigma_f;
+  const uint16_t* src;
+  const float* z;
+  int64_t B;
+  int N, Nf;
+  bool merged;
+};
+inline CompositeSamples dense_samples(const float* rgb, const float* sigma, const float* z, int64_t B, int N) {
+  return {rgb, sigma, nullptr, nullptr, nullptr, z, B, N, 0, false};
+}
+inline CompositeSamples merged_samples(const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                                       const float* sigma_f, const uint16_t* src, const float* z_all, int64_t B, int N,
+                                       int Nf) {
+  return {rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, B, N, Nf, true};
+}
+// The opacity output and the background blend (composite.hip): bg null = no blend, else
+// bg + stride * r is ray r's colour (stride 0: one colour, 3: one per ray); bd NaN = the normalised
+// depth, else the depth of the background; acc_map (B) nullable.
 struct CompositeBg {
   const float* bg;
   int stride;
   float bd;
   float* acc_map;
 };
-int launch_composite_bg(const float* rgb, const float* sigma, const float* z, int64_t B, int N, float* rgb_map,
-                        float* depth, float* weights, const CompositeBg& bga, hipStream_t s);
-int launch_composite_merged_bg(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
-                               const uint16_t* src, const float* z_all, int64_t B, int N, int Nf, float* rgb_map,
-                               float* depth, float* weights, const CompositeBg& bga, hipStream_t s);
+// weights (B, N or T) nullable; bga null: composite_kernel, else composite_bg_kernel
+int launch_composite(const CompositeSamples& in, float* rgb_map, float* depth, float* weights, const CompositeBg* bga,
+                     hipStream_t s);
 
 }  // namespace nerf

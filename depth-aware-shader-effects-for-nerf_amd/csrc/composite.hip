@@ -26,6 +26,7 @@
 // wave per ray with 64-lane shuffle scans and reductions through ds_bpermute ran 0.50 / 0.88 ms for
 // the 800^2 coarse / fine composite, 0.28 of HBM bandwidth: it was bound by the cross-lane traffic.)
 #include "common.h"
+#include "composite_plan.h"
 
 namespace nerf {
 
@@ -70,8 +71,8 @@ struct MergedSrc {
 // STAGE (MERGED, T <= kStageT): 8 rays per block; their coarse and fine (rgb, sigma) are first copied
 // into LDS as one (r, g, b, sigma) quad per cat index, with whole-row coalesced loads, and the
 // composite gathers from there (gathering each sample's 16 bytes from global memory cost 1.14 ms
-// for the 800^2 fine pass against 0.18 ms of staging).
-constexpr int kStageT = 256;
+// for the 800^2 fine pass against 0.18 ms of staging).  Which variant, grid, block and LDS a call takes:
+// composite_plan.h (kStageT is there).
 
 // composite_bg_kernel: the ray's opacity acc = (float) sum w, the composite's own
 // double sum rounded once, goes to acc_map (nullable), and with k = max(0, 1 - acc)
@@ -88,89 +89,36 @@ constexpr int kStageT = 256;
 #include "composite_body.h"
 #undef COMPOSITE_BG
 
-int launch_composite(const float* rgb, const float* sigma, const float* z, int64_t B, int N, float* rgb_map,
-                     float* depth, float* weights, hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  const bool vec = N % 4 == 0 && (uintptr_t)rgb % 16 == 0 && (uintptr_t)sigma % 16 == 0 && (uintptr_t)z % 16 == 0 &&
-                   (!weights || (uintptr_t)weights % 16 == 0);
-  const dim3 grid((unsigned)((B + 15) / 16));
-  const MergedSrc none{};
-  if (vec)
-    hipLaunchKernelGGL((composite_kernel<true, false>), grid, dim3(256), 0, s, rgb, sigma, z, B, N, rgb_map, depth,
-                       weights, none);
+// One variant, plain or with the background (the same grid, block and LDS).  The merged forms take null
+// rgb / sigma and T as the kernel's N.
+template <bool VEC, bool MERGED, bool STAGE = false>
+static void launch_variant(const CompositePlan& p, const CompositeSamples& in, float* rgb_map, float* depth,
+                           float* weights, const CompositeBg* bga, hipStream_t s) {
+  const MergedSrc ms = MERGED ? MergedSrc{in.rgb, in.sigma, in.rgb_f, in.sigma_f, in.src, in.N, in.Nf} : MergedSrc{};
+  const float* rgb = MERGED ? nullptr : in.rgb;
+  const float* sigma = MERGED ? nullptr : in.sigma;
+  const int n = in.N + in.Nf;
+  if (bga)
+    hipLaunchKernelGGL((composite_bg_kernel<VEC, MERGED, STAGE>), dim3(p.grid), dim3(p.block), p.lds, s, rgb, sigma,
+                       in.z, in.B, n, rgb_map, depth, weights, ms, *bga);
   else
-    hipLaunchKernelGGL((composite_kernel<false, false>), grid, dim3(256), 0, s, rgb, sigma, z, B, N, rgb_map, depth,
-                       weights, none);
-  return check_launch("composite_kernel");
+    hipLaunchKernelGGL((composite_kernel<VEC, MERGED, STAGE>), dim3(p.grid), dim3(p.block), p.lds, s, rgb, sigma, in.z,
+                       in.B, n, rgb_map, depth, weights, ms);
 }
 
-int launch_composite_merged(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
-                            const uint16_t* src, const float* z_all, int64_t B, int N, int Nf, float* rgb_map,
-                            float* depth, float* weights, hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  const int T = N + Nf;
-  const bool vec = T % 4 == 0 && (uintptr_t)z_all % 16 == 0 && (!weights || (uintptr_t)weights % 16 == 0);
-  const dim3 grid((unsigned)((B + 15) / 16));
-  const MergedSrc ms{rgb_c, sigma_c, rgb_f, sigma_f, src, N, Nf};
-  if (T <= kStageT) {
-    const size_t lds = (size_t)8 * T * sizeof(f32x4);
-    const dim3 grid8((unsigned)((B + 7) / 8));
-    if (vec)
-      hipLaunchKernelGGL((composite_kernel<true, true, true>), grid8, dim3(128), lds, s, nullptr, nullptr, z_all, B, T,
-                         rgb_map, depth, weights, ms);
-    else
-      hipLaunchKernelGGL((composite_kernel<false, true, true>), grid8, dim3(128), lds, s, nullptr, nullptr, z_all, B, T,
-                         rgb_map, depth, weights, ms);
-  } else if (vec)
-    hipLaunchKernelGGL((composite_kernel<true, true>), grid, dim3(256), 0, s, nullptr, nullptr, z_all, B, T, rgb_map,
-                       depth, weights, ms);
-  else
-    hipLaunchKernelGGL((composite_kernel<false, true>), grid, dim3(256), 0, s, nullptr, nullptr, z_all, B, T, rgb_map,
-                       depth, weights, ms);
-  return check_launch("composite_kernel (merged)");
-}
-
-// The same grids, blocks and LDS with composite_bg_kernel (the merged form stages whole rows as above).
-int launch_composite_bg(const float* rgb, const float* sigma, const float* z, int64_t B, int N, float* rgb_map,
-                        float* depth, float* weights, const CompositeBg& bga, hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  const bool vec = N % 4 == 0 && (uintptr_t)rgb % 16 == 0 && (uintptr_t)sigma % 16 == 0 && (uintptr_t)z % 16 == 0 &&
-                   (!weights || (uintptr_t)weights % 16 == 0);
-  const dim3 grid((unsigned)((B + 15) / 16));
-  const MergedSrc none{};
-  if (vec)
-    hipLaunchKernelGGL((composite_bg_kernel<true, false>), grid, dim3(256), 0, s, rgb, sigma, z, B, N, rgb_map, depth,
-                       weights, none, bga);
-  else
-    hipLaunchKernelGGL((composite_bg_kernel<false, false>), grid, dim3(256), 0, s, rgb, sigma, z, B, N, rgb_map, depth,
-                       weights, none, bga);
-  return check_launch("composite_bg_kernel");
-}
-
-int launch_composite_merged_bg(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
-                               const uint16_t* src, const float* z_all, int64_t B, int N, int Nf, float* rgb_map,
-                               float* depth, float* weights, const CompositeBg& bga, hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  const int T = N + Nf;
-  const bool vec = T % 4 == 0 && (uintptr_t)z_all % 16 == 0 && (!weights || (uintptr_t)weights % 16 == 0);
-  const dim3 grid((unsigned)((B + 15) / 16));
-  const MergedSrc ms{rgb_c, sigma_c, rgb_f, sigma_f, src, N, Nf};
-  if (T <= kStageT) {
-    const size_t lds = (size_t)8 * T * sizeof(f32x4);
-    const dim3 grid8((unsigned)((B + 7) / 8));
-    if (vec)
-      hipLaunchKernelGGL((composite_bg_kernel<true, true, true>), grid8, dim3(128), lds, s, nullptr, nullptr, z_all, B,
-                         T, rgb_map, depth, weights, ms, bga);
-    else
-      hipLaunchKernelGGL((composite_bg_kernel<false, true, true>), grid8, dim3(128), lds, s, nullptr, nullptr, z_all, B,
-                         T, rgb_map, depth, weights, ms, bga);
-  } else if (vec)
-    hipLaunchKernelGGL((composite_bg_kernel<true, true>), grid, dim3(256), 0, s, nullptr, nullptr, z_all, B, T, rgb_map,
-                       depth, weights, ms, bga);
-  else
-    hipLaunchKernelGGL((composite_bg_kernel<false, true>), grid, dim3(256), 0, s, nullptr, nullptr, z_all, B, T,
-                       rgb_map, depth, weights, ms, bga);
-  return check_launch("composite_bg_kernel (merged)");
+int launch_composite(const CompositeSamples& in, float* rgb_map, float* depth, float* weights, const CompositeBg* bga,
+                     hipStream_t s) {
+  const CompositePlan p = composite_forward_plan(in.B, in.N, in.Nf, in.merged, in.rgb, in.sigma, in.z, weights, bga);
+  if (p.action == CompositePlan::kSkip) return NERF_OK;
+  switch (p.vec | p.stage << 1 | p.merged << 2) {   // (STAGE is a merged variant)
+    case 0: launch_variant<false, false>(p, in, rgb_map, depth, weights, bga, s); break;
+    case 1: launch_variant<true, false>(p, in, rgb_map, depth, weights, bga, s); break;
+    case 4: launch_variant<false, true>(p, in, rgb_map, depth, weights, bga, s); break;
+    case 5: launch_variant<true, true>(p, in, rgb_map, depth, weights, bga, s); break;
+    case 6: launch_variant<false, true, true>(p, in, rgb_map, depth, weights, bga, s); break;
+    case 7: launch_variant<true, true, true>(p, in, rgb_map, depth, weights, bga, s); break;
+  }
+  return check_launch(p.name);
 }
 
 }  // namespace nerf

@@ -7,6 +7,7 @@
 //   composite_merged_backward_kernel   the same over the N + Nf merged samples of the hierarchical
 //                               step, gathered from and written back to the coarse and fine rows
 //                               through LDS
+#include "composite_plan.h"
 #include "train_internal.h"
 
 namespace nerf {
@@ -40,9 +41,8 @@ namespace nerf {
 // and a quad is last read when its sample's results are formed), and the quads go back to the split
 // rows as whole coalesced rows.  Every output element has one writer.  Coarse rows take in + term
 // when `accumulate` is set (the coarse composite's own term is already there), fine rows are always
-// written.  LDS: 16 T bytes per ray; the launcher puts 4 rays in a block up to T = 768 and 2 beyond
-// (40 KB at kMergedBwdMaxT).
-constexpr int kMergedBwdMaxT = 1280;          // N <= 256, Nf <= 1024 (the resampler's limits)
+// written.  LDS: 16 T bytes per ray; composite_plan.h puts 4 rays in a block up to T = 768 and 2 beyond
+// (40 KB at its kMergedBwdMaxT).
 constexpr int kMergedBwdChunks = kMergedBwdMaxT / 64;
 
 #define COMPOSITE_BWD_ACC 0   // (the kernels, twice: composite_bwd_body.h)
@@ -52,60 +52,36 @@ constexpr int kMergedBwdChunks = kMergedBwdMaxT / 64;
 #include "composite_bwd_body.h"
 #undef COMPOSITE_BWD_ACC
 
-int launch_composite_backward(const float* rgb, const float* sigma, const float* z, const float* rgb_map,
-                              const float* target, const float* grad_map, const float* grad_depth, int64_t B, int N,
-                              float scale, float* dsigma, float* drgb, float* sq_err, hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  hipLaunchKernelGGL(composite_backward_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, rgb, sigma, z,
-                     rgb_map, target, grad_map, grad_depth, B, N, scale, dsigma, drgb, sq_err);
-  return check_launch("composite_backward_kernel");
-}
-
-// the gradient form with an opacity gradient g_acc (nullable) and the forward's background depth bd (NaN: none)
-int launch_composite_backward_acc(const float* rgb, const float* sigma, const float* z, const float* grad_map,
-                                  const float* grad_depth, const float* g_acc, float bd, int64_t B, int N,
-                                  float* dsigma, float* drgb, hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  hipLaunchKernelGGL(composite_backward_acc_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, rgb, sigma, z,
-                     (const float*)nullptr, (const float*)nullptr, grad_map, grad_depth, B, N, 0.0f, dsigma, drgb,
-                     (float*)nullptr, g_acc, bd);
-  return check_launch("composite_backward_acc_kernel");
-}
-
-int launch_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f,
-                                     const float* sigma_f, const uint16_t* src, const float* z_all,
-                                     const float* rgb_map, const float* target, const float* grad_map,
-                                     const float* grad_depth, int64_t B, int N, int Nf, float scale, int accumulate,
-                                     float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f, float* sq_err,
-                                     hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  const int T = N + Nf;
-  if (N < 1 || Nf < 1 || T > kMergedBwdMaxT)
-    return set_error(NERF_ERR_UNSUPPORTED, "composite_merged_backward: N=%d Nf=%d (N + Nf <= %d)", N, Nf, kMergedBwdMaxT);
-  const int rpb = T <= 768 ? 4 : 2;   // rays per block: at most 48 KB of LDS
-  const size_t lds = (size_t)rpb * T * sizeof(f32x4);
-  hipLaunchKernelGGL(composite_merged_backward_kernel, dim3((unsigned)((B + rpb - 1) / rpb)), dim3(64 * rpb), lds, s,
-                     rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, rgb_map, target, grad_map, grad_depth, B, N, Nf, scale,
-                     accumulate, dsigma_c, drgb_c, dsigma_f, drgb_f, sq_err);
-  return check_launch("composite_merged_backward_kernel");
-}
-
-int launch_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c, const float* rgb_f,
-                                         const float* sigma_f, const uint16_t* src, const float* z_all,
-                                         const float* grad_map, const float* grad_depth, const float* g_acc, float bd,
-                                         int64_t B, int N, int Nf, int accumulate, float* dsigma_c, float* drgb_c,
-                                         float* dsigma_f, float* drgb_f, hipStream_t s) {
-  if (B == 0) return NERF_OK;
-  const int T = N + Nf;
-  if (N < 1 || Nf < 1 || T > kMergedBwdMaxT)
-    return set_error(NERF_ERR_UNSUPPORTED, "composite_merged_backward: N=%d Nf=%d (N + Nf <= %d)", N, Nf, kMergedBwdMaxT);
-  const int rpb = T <= 768 ? 4 : 2;   // rays per block: at most 48 KB of LDS
-  const size_t lds = (size_t)rpb * T * sizeof(f32x4);
-  hipLaunchKernelGGL(composite_merged_backward_acc_kernel, dim3((unsigned)((B + rpb - 1) / rpb)), dim3(64 * rpb), lds, s,
-                     rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, (const float*)nullptr, (const float*)nullptr, grad_map,
-                     grad_depth, B, N, Nf, 0.0f, accumulate, dsigma_c, drgb_c, dsigma_f, drgb_f, (float*)nullptr, g_acc,
-                     bd);
-  return check_launch("composite_merged_backward_acc_kernel");
+int launch_composite_backward(const CompositeSamples& in, const CompositeUpstream& up, const CompositeAccGrad* acc,
+                              const CompositeGrads& out, hipStream_t s) {
+  const CompositePlan p = composite_backward_plan(in.B, in.N, in.Nf, in.merged, acc != nullptr);
+  if (p.action == CompositePlan::kSkip) return NERF_OK;
+  if (p.action == CompositePlan::kRefuse)
+    return set_error(NERF_ERR_UNSUPPORTED, "composite_merged_backward: N=%d Nf=%d (N + Nf <= %d)", in.N, in.Nf,
+                     kMergedBwdMaxT);
+  const dim3 grid(p.grid), block(p.block);
+  switch (p.merged << 1 | p.alt) {
+    case 0:
+      hipLaunchKernelGGL(composite_backward_kernel, grid, block, p.lds, s, in.rgb, in.sigma, in.z, up.rgb_map, up.target,
+                         up.grad_map, up.grad_depth, in.B, in.N, up.scale, out.dsigma, out.drgb, up.sq_err);
+      break;
+    case 1:
+      hipLaunchKernelGGL(composite_backward_acc_kernel, grid, block, p.lds, s, in.rgb, in.sigma, in.z, up.rgb_map,
+                         up.target, up.grad_map, up.grad_depth, in.B, in.N, up.scale, out.dsigma, out.drgb, up.sq_err,
+                         acc->g_acc, acc->bd);
+      break;
+    case 2:
+      hipLaunchKernelGGL(composite_merged_backward_kernel, grid, block, p.lds, s, in.rgb, in.sigma, in.rgb_f, in.sigma_f,
+                         in.src, in.z, up.rgb_map, up.target, up.grad_map, up.grad_depth, in.B, in.N, in.Nf, up.scale,
+                         out.accumulate, out.dsigma, out.drgb, out.dsigma_f, out.drgb_f, up.sq_err);
+      break;
+    case 3:
+      hipLaunchKernelGGL(composite_merged_backward_acc_kernel, grid, block, p.lds, s, in.rgb, in.sigma, in.rgb_f,
+                         in.sigma_f, in.src, in.z, up.rgb_map, up.target, up.grad_map, up.grad_depth, in.B, in.N, in.Nf,
+                         up.scale, out.accumulate, out.dsigma, out.drgb, out.dsigma_f, out.drgb_f, up.sq_err, acc->g_acc,
+                         acc->bd);
+  }
+  return check_launch(p.name);
 }
 
 // ------------------------------------------------------------- background loss

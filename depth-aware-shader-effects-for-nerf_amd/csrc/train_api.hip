@@ -34,6 +34,9 @@ struct TrainWs {
   int* live;             // the occupancy tail (null without a grid)
   uint32_t* blocks;
   float *sigma_live, *rgb_live, *dsigma_live, *drgb_live;
+  // the part's dense sample set and where its composite backward writes
+  CompositeSamples samples(int64_t B, int N) const { return dense_samples(rgb, sigma, z, B, N); }
+  CompositeGrads grads() const { return {dsigma, drgb, nullptr, nullptr, 0}; }
 };
 
 // one sample set's regions, dirs .. grad (the hierarchical step carves two of them)
@@ -121,6 +124,11 @@ struct HierWs {
   uint16_t* src;
   float *grad2, *dapp2, *wgrad;
   size_t wgrad_floats;
+  // the merged sample set; its backward adds to the coarse rows (the coarse composite's term is there)
+  CompositeSamples merged(int64_t B, int N, int Nf) const {
+    return merged_samples(c.rgb, c.sigma, f.rgb, f.sigma, src, z_all, B, N, Nf);
+  }
+  CompositeGrads merged_grads() const { return {c.dsigma, c.drgb, f.dsigma, f.drgb, 1}; }
 };
 
 static bool hier_shape_ok(int64_t B, int N, int Nf) {
@@ -206,22 +214,23 @@ static BgScratch bg_scratch(float* grad_rows, int64_t B) {
 }
 static_assert(kGradRow >= 6 * 64, "the head's per-ray scratch fits in a ray's gradient rows");
 
-// One sample set's head from its per-ray gradient (g_rgb, g_acc) and the two means; `composite_acc`
-// recomputes the opacity of the rows the forward left (its maps go to the set's unused `maps` region),
-// `composite_backward` is the set's composite backward in its _acc form.
-template <typename Acc, typename Bwd>
-static int backward_head_bg(const TrainWs& w, const float* rgb_map, const float* target, int64_t B, const BgLoss& o,
-                            double weight, float* loss_rgb, float* loss_acc, float* rgb_final, Acc&& composite_acc,
-                            Bwd&& composite_backward, hipStream_t s) {
+// The head of sample set `in` (its per-ray regions are w's) from its per-ray gradient (g_rgb, g_acc), and
+// the two means: the composite once more for the opacity of the rows the forward left (its maps go to the
+// set's unused `maps` region), the per-ray loss, the composite backward in its _acc form into `out`.
+static int backward_head_bg(const TrainWs& w, const CompositeSamples& in, const CompositeGrads& out,
+                            const float* rgb_map, const float* target, const BgLoss& o, double weight, float* loss_rgb,
+                            float* loss_acc, float* rgb_final, hipStream_t s) {
+  const int64_t B = in.B;
   const BgScratch t = bg_scratch(w.grad, B);
   const CompositeBg acc_only{nullptr, 0, __builtin_nanf(""), t.acc};
+  const CompositeAccGrad acc{t.g_acc, __builtin_nanf("")};
   int rc;
-  if ((rc = composite_acc(w.maps, w.maps + 3 * B, acc_only))) return rc;
+  if ((rc = launch_composite(in, w.maps, w.maps + 3 * B, nullptr, &acc_only, s))) return rc;
   if ((rc = launch_bg_loss(rgb_map, t.acc, target, o.alpha, o.bg_rows ? o.bg : nullptr, o.bg_rows > 1 ? 3 : 0,
                            (float)o.acc_weight, (float)(weight * 2.0 / (3.0 * (double)B)),
                            (float)(weight * 2.0 / (double)B), B, t.g_rgb, t.g_acc, w.sq_err, t.sq_acc, rgb_final, s)))
     return rc;
-  if ((rc = composite_backward(t.g_rgb, t.g_acc))) return rc;
+  if ((rc = launch_composite_backward(in, upstream_grad(t.g_rgb, nullptr), &acc, out, s))) return rc;
   if ((rc = launch_loss(w.sq_err, B, loss_rgb, s))) return rc;
   return launch_loss_rays(t.sq_acc, B, loss_acc, s);
 }
@@ -274,8 +283,8 @@ int nerf_composite_backward(const float* rgb, const float* sigma, const float* z
   if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward: N=%d (1..4096)", N);
   REQUIRE(B == 0 || (rgb && sigma && z_vals && rgb_map && target && dsigma && drgb && sq_err),
           "nerf_composite_backward: null pointer");
-  return launch_composite_backward(rgb, sigma, z_vals, rgb_map, target, nullptr, nullptr, B, N, scale, dsigma, drgb,
-                                   sq_err, (hipStream_t)stream);
+  return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_loss(rgb_map, target, scale, sq_err),
+                                   nullptr, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
 }
 
 int nerf_composite_backward_grad(const float* rgb, const float* sigma, const float* z_vals, const float* grad_rgb_map,
@@ -284,8 +293,8 @@ int nerf_composite_backward_grad(const float* rgb, const float* sigma, const flo
   REQUIRE(B >= 0, "nerf_composite_backward_grad: B=%lld", (long long)B);
   if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward_grad: N=%d (1..4096)", N);
   REQUIRE(B == 0 || (rgb && sigma && z_vals && dsigma && drgb), "nerf_composite_backward_grad: null pointer");
-  return launch_composite_backward(rgb, sigma, z_vals, nullptr, nullptr, grad_rgb_map, grad_depth_map, B, N, 0.0f,
-                                   dsigma, drgb, nullptr, (hipStream_t)stream);
+  return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_grad(grad_rgb_map, grad_depth_map),
+                                   nullptr, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
 }
 
 int nerf_mlp_backward(const float* packed, const float* packedT, const float* save, const uint32_t* masks,
@@ -577,7 +586,7 @@ static int check_backward_ptrs(const char* fn, const float* packed, const float*
 // the forward's tail: the composite (render.py:56-80) and the optional copy of z
 static int forward_tail(const char* fn, const TrainWs& w, int64_t B, int N, float* rgb_map, float* depth_map,
                         float* weights_out, float* z_out, hipStream_t s) {
-  if (int rc = launch_composite(w.rgb, w.sigma, w.z, B, N, rgb_map, depth_map, weights_out, s)) return rc;
+  if (int rc = launch_composite(w.samples(B, N), rgb_map, depth_map, weights_out, nullptr, s)) return rc;
   if (z_out && hipMemcpyAsync(z_out, w.z, (size_t)B * N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
     return set_error(NERF_ERR_HIP, "%s: z copy failed", fn);
   return NERF_OK;
@@ -587,25 +596,10 @@ static int forward_tail(const char* fn, const TrainWs& w, int64_t B, int N, floa
 static int backward_head(const TrainWs& w, const float* rgb_map, const float* target, int64_t B, int N, float* loss,
                          hipStream_t s) {
   const float scale = (float)(2.0 / (3.0 * (double)B));
-  if (int rc = launch_composite_backward(w.rgb, w.sigma, w.z, rgb_map, target, nullptr, nullptr, B, N, scale, w.dsigma,
-                                         w.drgb, w.sq_err, s))
+  if (int rc = launch_composite_backward(w.samples(B, N), upstream_loss(rgb_map, target, scale, w.sq_err), nullptr,
+                                         w.grads(), s))
     return rc;
   return launch_loss(w.sq_err, B, loss, s);
-}
-
-// the dense rows' head (nerf_train_backward_bg and, on the zero-filled dense rows, the occupancy one)
-static int backward_head_dense_bg(const TrainWs& w, const float* rgb_map, const float* target, int64_t B, int N,
-                                  const BgLoss& o, float* loss, float* rgb_final, hipStream_t s) {
-  return backward_head_bg(
-      w, rgb_map, target, B, o, 1.0, loss, loss + 1, rgb_final,
-      [&](float* m_rgb, float* m_depth, const CompositeBg& a) {
-        return launch_composite_bg(w.rgb, w.sigma, w.z, B, N, m_rgb, m_depth, nullptr, a, s);
-      },
-      [&](const float* g_rgb, const float* g_acc) {
-        return launch_composite_backward_acc(w.rgb, w.sigma, w.z, g_rgb, nullptr, g_acc, __builtin_nanf(""), B, N, w.dsigma,
-                                             w.drgb, s);
-      },
-      s);
 }
 
 // with every option off: the opacity parts of the loss read 0 and rgb_final is rgb_map
@@ -617,6 +611,16 @@ static int bg_off_outputs(const char* fn, float* loss_acc, int n_acc, float* rgb
       hipMemcpyAsync(rgb_final, rgb_map, (size_t)B * 12, hipMemcpyDeviceToDevice, s) != hipSuccess)
     return set_error(NERF_ERR_HIP, "%s: rgb_final copy failed", fn);
   return NERF_OK;
+}
+
+// The head of the dense step and, on its zero-filled dense rows (a dead sample has weight 0), of the
+// occupancy step; bgl null: the entry without a background.
+static int dense_head(const char* fn, const TrainWs& w, const float* rgb_map, const float* target, int64_t B, int N,
+                      const BgLoss* bgl, float* loss, float* rgb_final, hipStream_t s) {
+  if (bgl && !bgl->off())
+    return backward_head_bg(w, w.samples(B, N), w.grads(), rgb_map, target, *bgl, 1.0, loss, loss + 1, rgb_final, s);
+  if (int rc = backward_head(w, rgb_map, target, B, N, loss, s)) return rc;
+  return bgl ? bg_off_outputs(fn, loss + 1, 1, rgb_final, rgb_map, B, s) : NERF_OK;
 }
 
 size_t nerf_train_workspace_bytes(int64_t B, int N) {
@@ -683,12 +687,7 @@ static int train_backward(const char* fn, const float* packed, const float* pack
     return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_forward wrote this workspace", fn);
   const uint32_t* masks = fwd.arith == NERF_ARITH_F16X3 ? w.masks : nullptr;
   const int64_t M = B * N;
-  if (bgl && !bgl->off()) {
-    if ((rc = backward_head_dense_bg(w, rgb_map, target, B, N, *bgl, loss, rgb_final, s))) return rc;
-  } else {
-    if ((rc = backward_head(w, rgb_map, target, B, N, loss, s))) return rc;
-    if (bgl && (rc = bg_off_outputs(fn, loss + 1, 1, rgb_final, rgb_map, B, s))) return rc;
-  }
+  if ((rc = dense_head(fn, w, rgb_map, target, B, N, bgl, loss, rgb_final, s))) return rc;
   if ((rc = launch_mlp_backward(packed, packedT, w.save, masks, w.sigma, w.rgb, w.dsigma, w.drgb, M, w.grad, s,
                                 /*store_dhd=*/!fused_ray_sums(N))))
     return rc;
@@ -772,12 +771,7 @@ static int train_occ_backward(const char* fn, const float* packed, const float* 
     return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_occ_forward with M_live=%lld wrote this "
                      "workspace", fn, (long long)M_live);
   hipStream_t s = (hipStream_t)stream;
-  if (bgl && !bgl->off()) {   // (on the dense zero-filled rows: a dead sample has weight 0)
-    if ((rc = backward_head_dense_bg(w, rgb_map, target, B, N, *bgl, loss, rgb_final, s))) return rc;
-  } else {
-    if ((rc = backward_head(w, rgb_map, target, B, N, loss, s))) return rc;
-    if (bgl && (rc = bg_off_outputs(fn, loss + 1, 1, rgb_final, rgb_map, B, s))) return rc;
-  }
+  if ((rc = dense_head(fn, w, rgb_map, target, B, N, bgl, loss, rgb_final, s))) return rc;
   if (M_live == 0) {   // every sample dead: sigma = 0 is a constant of the step, every gradient is zero
     for (int p = 0; p < P_COUNT; ++p)
       if (hipMemsetAsync(param_grads_out[p], 0, param_floats(p) * 4, s) != hipSuccess)
@@ -860,7 +854,7 @@ int nerf_train_hier_forward(const float* packed, const float* rays_o, const floa
     return rc;
   remember_forward(workspace, {g_mlp_arith, kStepHier, 0});
   float* wc = coarse_weights_out ? coarse_weights_out : h.w_c;
-  if ((rc = launch_composite(c.rgb, c.sigma, c.z, B, N, coarse_rgb, coarse_depth, wc, s))) return rc;
+  if ((rc = launch_composite(c.samples(B, N), coarse_rgb, coarse_depth, wc, nullptr, s))) return rc;
   // the resample (the draws of nerf_render_rays at ray0 = 0), the Nf new samples, the merged composite
   if ((rc = launch_importance(nullptr, nullptr, c.z, wc, B, N, Nf, u_lin, u_rand, seed ^ 0x5DEECE66Dull, h.z_all, nullptr,
                               nullptr, nullptr, nullptr, nullptr, f.z, nullptr, s, h.src)))
@@ -868,9 +862,7 @@ int nerf_train_hier_forward(const float* packed, const float* rays_o, const floa
   if ((rc = launch_mlp(packed, rays_o, c.dirs, f.z, B, Nf, c.feat, f.rgb, f.sigma, nullptr, 0, s, f.save, c.encd,
                        f.masks)))
     return rc;
-  if ((rc = launch_composite_merged(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, B, N, Nf, rgb_map, depth_map,
-                                    weights_out, s)))
-    return rc;
+  if ((rc = launch_composite(h.merged(B, N, Nf), rgb_map, depth_map, weights_out, nullptr, s))) return rc;
   if (z_out && hipMemcpyAsync(z_out, h.z_all, (size_t)B * (N + Nf) * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
     return set_error(NERF_ERR_HIP, "%s: z copy failed", fn);
   return NERF_OK;
@@ -906,38 +898,19 @@ static int train_hier_backward(const char* fn, const float* packed, const float*
   if (bgl && !bgl->off()) {
     // the same two terms from each part's per-ray head (the coarse part's scaled by coarse_weight); loss:
     // fine colour, coarse colour, fine opacity, coarse opacity
-    const float nan = __builtin_nanf("");
-    if ((rc = backward_head_bg(
-             c, coarse_rgb, target, B, *bgl, coarse_weight, loss + 1, loss + 3, coarse_final,
-             [&](float* m_rgb, float* m_depth, const CompositeBg& a) {
-               return launch_composite_bg(c.rgb, c.sigma, c.z, B, N, m_rgb, m_depth, nullptr, a, s);
-             },
-             [&](const float* g_rgb, const float* g_acc) {
-               return launch_composite_backward_acc(c.rgb, c.sigma, c.z, g_rgb, nullptr, g_acc, nan, B, N, c.dsigma,
-                                                    c.drgb, s);
-             },
-             s)))
+    if ((rc = backward_head_bg(c, c.samples(B, N), c.grads(), coarse_rgb, target, *bgl, coarse_weight, loss + 1,
+                               loss + 3, coarse_final, s)))
       return rc;
-    if ((rc = backward_head_bg(
-             f, rgb_map, target, B, *bgl, 1.0, loss, loss + 2, rgb_final,
-             [&](float* m_rgb, float* m_depth, const CompositeBg& a) {
-               return launch_composite_merged_bg(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, B, N, Nf, m_rgb, m_depth,
-                                                 nullptr, a, s);
-             },
-             [&](const float* g_rgb, const float* g_acc) {
-               return launch_composite_merged_backward_acc(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, g_rgb, nullptr,
-                                                           g_acc, nan, B, N, Nf, 1, c.dsigma, c.drgb, f.dsigma, f.drgb,
-                                                           s);
-             },
-             s)))
+    if ((rc = backward_head_bg(f, h.merged(B, N, Nf), h.merged_grads(), rgb_map, target, *bgl, 1.0, loss, loss + 2,
+                               rgb_final, s)))
       return rc;
   } else {
-    if ((rc = launch_composite_backward(c.rgb, c.sigma, c.z, coarse_rgb, target, nullptr, nullptr, B, N,
-                                        (float)(coarse_weight * mse_scale), c.dsigma, c.drgb, c.sq_err, s)))
+    if ((rc = launch_composite_backward(c.samples(B, N),
+                                        upstream_loss(coarse_rgb, target, (float)(coarse_weight * mse_scale), c.sq_err),
+                                        nullptr, c.grads(), s)))
       return rc;
-    if ((rc = launch_composite_merged_backward(c.rgb, c.sigma, f.rgb, f.sigma, h.src, h.z_all, rgb_map, target,
-                                               nullptr, nullptr, B, N, Nf, (float)mse_scale, 1, c.dsigma, c.drgb,
-                                               f.dsigma, f.drgb, f.sq_err, s)))
+    if ((rc = launch_composite_backward(h.merged(B, N, Nf), upstream_loss(rgb_map, target, (float)mse_scale, f.sq_err),
+                                        nullptr, h.merged_grads(), s)))
       return rc;
     if ((rc = launch_loss(f.sq_err, B, loss, s))) return rc;
     if ((rc = launch_loss(c.sq_err, B, loss + 1, s))) return rc;
@@ -1006,8 +979,9 @@ int nerf_composite_backward_grad_acc(const float* rgb, const float* sigma, const
   REQUIRE(B >= 0, "nerf_composite_backward_grad_acc: B=%lld", (long long)B);
   if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward_grad_acc: N=%d (1..4096)", N);
   REQUIRE(B == 0 || (rgb && sigma && z_vals && dsigma && drgb), "nerf_composite_backward_grad_acc: null pointer");
-  return launch_composite_backward_acc(rgb, sigma, z_vals, grad_rgb_map, grad_depth_map, g_acc, bd, B, N, dsigma, drgb,
-                                       (hipStream_t)stream);
+  const CompositeAccGrad acc{g_acc, bd};
+  return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_grad(grad_rgb_map, grad_depth_map),
+                                   &acc, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
 }
 
 int nerf_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c, const float* rgb_f,
@@ -1020,9 +994,10 @@ int nerf_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c,
     return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_merged_backward_acc: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
   REQUIRE(B == 0 || (rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c && drgb_c && dsigma_f && drgb_f),
           "nerf_composite_merged_backward_acc: null pointer");
-  return launch_composite_merged_backward_acc(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, grad_rgb_map, grad_depth_map,
-                                              g_acc, bd, B, N, Nf, accumulate_coarse, dsigma_c, drgb_c, dsigma_f, drgb_f,
-                                              (hipStream_t)stream);
+  const CompositeAccGrad acc{g_acc, bd};
+  return launch_composite_backward(merged_samples(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, B, N, Nf),
+                                   upstream_grad(grad_rgb_map, grad_depth_map), &acc,
+                                   {dsigma_c, drgb_c, dsigma_f, drgb_f, accumulate_coarse}, (hipStream_t)stream);
 }
 
 int nerf_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
@@ -1035,9 +1010,9 @@ int nerf_composite_merged_backward(const float* rgb_c, const float* sigma_c, con
     return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_merged_backward: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
   REQUIRE(B == 0 || (rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c && drgb_c && dsigma_f && drgb_f),
           "nerf_composite_merged_backward: null pointer");
-  return launch_composite_merged_backward(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, nullptr, nullptr, grad_rgb_map,
-                                          grad_depth_map, B, N, Nf, 0.0f, accumulate_coarse, dsigma_c, drgb_c, dsigma_f,
-                                          drgb_f, nullptr, (hipStream_t)stream);
+  return launch_composite_backward(merged_samples(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, B, N, Nf),
+                                   upstream_grad(grad_rgb_map, grad_depth_map), nullptr,
+                                   {dsigma_c, drgb_c, dsigma_f, drgb_f, accumulate_coarse}, (hipStream_t)stream);
 }
 
 int nerf_sample_importance_src(const float* z_vals, const float* weights, int64_t B, int N, int Nf, const float* u_lin,

@@ -66,28 +66,37 @@ inline size_t ray_sum_b_floats(int64_t M) { return (size_t)(M / 32 + 1) * kDirHi
 inline size_t ray_sum_floats(int64_t M) { return ray_sum_a_floats(M) + ray_sum_b_floats(M) + (size_t)(M / 32 + 1) * 32 + 64; }
 
 // ------------------------------------------------------------------------------- launchers
-// composite_bwd.hip
-int launch_composite_backward(const float* rgb, const float* sigma, const float* z, const float* rgb_map,
-                              const float* target, const float* grad_map, const float* grad_depth, int64_t B, int N,
-                              float scale, float* dsigma, float* drgb, float* sq_err, hipStream_t s);
-// the same over the merged samples of the hierarchical step (sample p of ray r: src[r (N + Nf) + p] of
-// cat[coarse, fine]); coarse rows take in + term when `accumulate` is set
-int launch_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f,
-                                     const float* sigma_f, const uint16_t* src, const float* z_all,
-                                     const float* rgb_map, const float* target, const float* grad_map,
-                                     const float* grad_depth, int64_t B, int N, int Nf, float scale, int accumulate,
-                                     float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f, float* sq_err,
-                                     hipStream_t s);
-// the gradient forms with an opacity gradient g_acc (B, nullable = 0: added to every dw of the ray) and the
-// forward's background depth bd (NaN: the normalised depth): composite_bwd_body.h, DESIGN.md §15
-int launch_composite_backward_acc(const float* rgb, const float* sigma, const float* z, const float* grad_map,
-                                  const float* grad_depth, const float* g_acc, float bd, int64_t B, int N,
-                                  float* dsigma, float* drgb, hipStream_t s);
-int launch_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c, const float* rgb_f,
-                                         const float* sigma_f, const uint16_t* src, const float* z_all,
-                                         const float* grad_map, const float* grad_depth, const float* g_acc, float bd,
-                                         int64_t B, int N, int Nf, int accumulate, float* dsigma_c, float* drgb_c,
-                                         float* dsigma_f, float* drgb_f, hipStream_t s);
+// composite_bwd.hip: the composite backward over a sample set (CompositeSamples, common.h).
+// The upstream gradient, one of two forms: the MSE against target (g = scale (rgb_map - target), sq_err (B)
+// takes the squared errors), or given gradients of rgb_map (B,3) and depth_map (B), each nullable = 0.
+struct CompositeUpstream {
+  const float *rgb_map, *target;
+  float scale;
+  float* sq_err;
+  const float *grad_map, *grad_depth;
+};
+inline CompositeUpstream upstream_loss(const float* rgb_map, const float* target, float scale, float* sq_err) {
+  return {rgb_map, target, scale, sq_err, nullptr, nullptr};
+}
+inline CompositeUpstream upstream_grad(const float* grad_map, const float* grad_depth) {
+  return {nullptr, nullptr, 0.0f, nullptr, grad_map, grad_depth};
+}
+// The opacity part (the _acc kernels: composite_bwd_body.h): g_acc (B, nullable = 0) is added
+// to every dw of the ray; bd is the forward's background depth (NaN: the normalised depth).
+struct CompositeAccGrad {
+  const float* g_acc;
+  float bd;
+};
+// d loss / d(sigma, rgb) per sample; a merged set also has the fine pair, and its coarse rows take
+// in + term when `accumulate` is set
+struct CompositeGrads {
+  float *dsigma, *drgb, *dsigma_f, *drgb_f;
+  int accumulate;
+};
+// acc null: the plain kernels, else the _acc ones (with the gradient form of `up`)
+int launch_composite_backward(const CompositeSamples& in, const CompositeUpstream& up, const CompositeAccGrad* acc,
+                              const CompositeGrads& out, hipStream_t s);
+
 // the per-ray loss head of a step with a background (composite_bwd.hip; the means: launch_loss / launch_loss_rays)
 int launch_bg_loss(const float* rgb_map, const float* acc, const float* target, const float* alpha, const float* bg,
                    int bg_stride, float acc_weight, float scale_rgb, float scale_acc, int64_t B, float* g_rgb,

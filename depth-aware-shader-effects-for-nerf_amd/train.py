@@ -264,6 +264,39 @@ class Trainer:
             self.view(self.grad, 20).zero_()
             self.view(self.grad, 21).zero_()
 
+    def _pack_for_step(self, main, B, app_idx):
+        """The step variants' prologue: both weight packings (the transposed one aside), the output maps
+        and the appearance row.  (rgb_map, depth, app, rows)"""
+        _lib.check(self.lib.nerf_pack_weights(self.param_ptrs, _lib.ptr(self.packed), _lib.stream()),
+                   "nerf_pack_weights")
+        self._pack_transposed_aside(main)
+        return self._maps(B) + self._app_row(app_idx)
+
+    def _backward(self, main, entry, args, ws, app_idx, rgb_map, bgo, hier=False):
+        """The step variants' epilogue: the join with the transposed packing, then the C entry `entry`
+        (`args`: what it takes between packedT and the gradient pointers, ending in app, rows) or, for a
+        trainer with a background, its _bg twin with `bgo` appended.  (loss, the map the loss was taken on)"""
+        P, rows = _lib.ptr, args[-1]
+        # d app of the batch's image goes straight into its row of the table's gradient
+        dapp = self.app_grad[int(app_idx)] if rows else None
+        main.wait_event(self._join)
+        if bgo is None:
+            lp = self.loss_parts if hier else self.loss_buf
+            tail, out = (), rgb_map
+        else:
+            al, bg, bg_rows, aw, out = bgo
+            entry, lp = entry + "_bg", self.loss_parts
+            tail = (P(al), P(bg), bg_rows, aw, P(out)) + ((None,) if hier else ())     # (no coarse_final)
+        _lib.check(getattr(self.lib, entry)(P(self.packed), P(self.packedT), *args, self.grad_ptrs, P(dapp), P(lp),
+                                            P(ws), ws.numel(), *tail, _lib.stream()), entry)
+        self._zero_unused_projection(rows)
+        # loss_parts: (colour, opacity), hierarchical (fine colour, coarse colour, fine opacity, coarse opacity)
+        if bgo is None:
+            return (lp[0] + self.coarse_loss_weight * lp[1] if hier else lp[0]), out
+        if hier:
+            return (lp[0] + aw * lp[2]) + self.coarse_loss_weight * (lp[1] + aw * lp[3]), out
+        return lp[0] + aw * lp[1], out
+
     # ------------------------------------------------------------------------------ one step
     def forward_backward(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, u_rand=None, seed=None,
                          alpha=None, _marks=None):
@@ -289,34 +322,18 @@ class Trainer:
             raise ValueError("Trainer: u_rand belongs to the fine pass; construct the trainer with hierarchical=True")
         if self.occupancy is not None:
             return self._forward_backward_occ(o, d, tgt, app_idx, t_rand, seed, _marks, bgo)
-        _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
         main = torch.cuda.current_stream(self.dev)
-        self._pack_transposed_aside(main)
+        rgb_map, depth, app, rows = self._pack_for_step(main, B, app_idx)
         t_vals = self._t_vals(N)
         ws = self._workspace(B, N)
-        rgb_map, depth = self._maps(B)
-        app, rows = self._app_row(app_idx)
         _lib.check(lib.nerf_train_forward(P(self.packed), P(o), P(d), B, self.near, self.far, N,
                                           P(t_vals), 1, P(t_rand), int(seed), P(app), rows, P(rgb_map),
                                           P(depth), None, None, P(ws), ws.numel(), s),
                    "nerf_train_forward")
         if _marks is not None:
             _marks[1].record(torch.cuda.current_stream())
-        # d app of the batch's image goes straight into its row of the table's gradient
-        dapp = self.app_grad[int(app_idx)] if rows else None
-        main.wait_event(self._join)
-        if bgo is not None:
-            al, bg, bg_rows, aw, final = bgo
-            _lib.check(lib.nerf_train_backward_bg(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, P(app),
-                                                  rows, self.grad_ptrs, P(dapp), P(self.loss_parts), P(ws), ws.numel(),
-                                                  P(al), P(bg), bg_rows, aw, P(final), s), "nerf_train_backward_bg")
-            self._zero_unused_projection(rows)
-            return self.loss_parts[0] + aw * self.loss_parts[1], final
-        _lib.check(lib.nerf_train_backward(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, P(app), rows,
-                                           self.grad_ptrs, P(dapp), P(self.loss_buf), P(ws), ws.numel(), s),
-                   "nerf_train_backward")
-        self._zero_unused_projection(rows)
-        return self.loss_buf[0], rgb_map
+        return self._backward(main, "nerf_train_backward", (P(rgb_map), P(tgt), B, N, P(app), rows), ws, app_idx,
+                              rgb_map, bgo)
 
     def _forward_backward_hier(self, o, d, tgt, app_idx, t_rand, u_rand, seed, _marks=None, bgo=None):
         """forward_backward with the fine pass: nerf_train_hier_forward + nerf_train_hier_backward on one
@@ -327,9 +344,8 @@ class Trainer:
         if u_rand is not None:
             u_rand = u_rand.to(self.dev, torch.float32).contiguous()
             assert u_rand.shape == (B, Nf)
-        _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
         main = torch.cuda.current_stream(self.dev)
-        self._pack_transposed_aside(main)
+        rgb_map, depth, app, rows = self._pack_for_step(main, B, app_idx)
         t_vals = self._t_vals(N)
         u_lin = linspace_table(Nf, self.dev, drop_last=True)        # ray_utils.py:115
         need = lib.nerf_train_hier_workspace_bytes(B, N, Nf)
@@ -339,32 +355,16 @@ class Trainer:
         if self._ws_hier is None or self._ws_hier.numel() < need:
             self._ws_hier = torch.empty(need, dtype=torch.uint8, device=self.dev)
         ws = self._ws_hier
-        rgb_map, depth = self._maps(B)
         rgb_c, depth_c = self._maps(B)
-        app, rows = self._app_row(app_idx)
         _lib.check(lib.nerf_train_hier_forward(P(self.packed), P(o), P(d), B, self.near, self.far, N, Nf, P(t_vals),
                                                P(u_lin), 1, P(t_rand), P(u_rand), int(seed), P(app), rows,
                                                P(rgb_map), P(depth), None, None, P(rgb_c), P(depth_c), None, P(ws),
                                                ws.numel(), s), "nerf_train_hier_forward")
         if _marks is not None:
             _marks[1].record(main)
-        dapp = self.app_grad[int(app_idx)] if rows else None
-        main.wait_event(self._join)
-        if bgo is not None:
-            al, bg, bg_rows, aw, final = bgo
-            _lib.check(lib.nerf_train_hier_backward_bg(P(self.packed), P(self.packedT), P(rgb_map), P(rgb_c), P(tgt), B,
-                                                       N, Nf, self.coarse_loss_weight, P(app), rows, self.grad_ptrs,
-                                                       P(dapp), P(self.loss_parts), P(ws), ws.numel(), P(al), P(bg),
-                                                       bg_rows, aw, P(final), None, s), "nerf_train_hier_backward_bg")
-            self._zero_unused_projection(rows)
-            lp, cw = self.loss_parts, self.coarse_loss_weight
-            return (lp[0] + aw * lp[2]) + cw * (lp[1] + aw * lp[3]), final
-        _lib.check(lib.nerf_train_hier_backward(P(self.packed), P(self.packedT), P(rgb_map), P(rgb_c), P(tgt), B, N, Nf,
-                                                self.coarse_loss_weight, P(app), rows, self.grad_ptrs, P(dapp),
-                                                P(self.loss_parts), P(ws), ws.numel(), s), "nerf_train_hier_backward")
-        self._zero_unused_projection(rows)
-        loss = self.loss_parts[0] + self.coarse_loss_weight * self.loss_parts[1]
-        return loss, rgb_map
+        return self._backward(main, "nerf_train_hier_backward",
+                              (P(rgb_map), P(rgb_c), P(tgt), B, N, Nf, self.coarse_loss_weight, P(app), rows), ws, app_idx,
+                              rgb_map, bgo, hier=True)
 
     def _forward_backward_occ(self, o, d, tgt, app_idx, t_rand, seed, _marks=None, bgo=None):
         """forward_backward on the live samples of self.occupancy: sample + classify, the live count
@@ -389,10 +389,7 @@ class Trainer:
                                              P(self._live_dev), P(ws), ws.numel(), s), "nerf_train_occ_sample")
         self._live_host.copy_(self._live_dev, non_blocking=True)
         self._live_ev.record(main)
-        _lib.check(lib.nerf_pack_weights(self.param_ptrs, P(self.packed), s), "nerf_pack_weights")
-        self._pack_transposed_aside(main)
-        rgb_map, depth = self._maps(B)
-        app, rows = self._app_row(app_idx)
+        rgb_map, depth, app, rows = self._pack_for_step(main, B, app_idx)
         self._live_ev.synchronize()                      # the step's one host wait
         m_live = int(self._live_host[0])
         self.live_fraction = m_live / max(1, B * N)
@@ -402,21 +399,8 @@ class Trainer:
                                               None, None, P(ws), ws.numel(), s), "nerf_train_occ_forward")
         if _marks is not None:
             _marks[1].record(main)
-        dapp = self.app_grad[int(app_idx)] if rows else None
-        main.wait_event(self._join)
-        if bgo is not None:
-            al, bg, bg_rows, aw, final = bgo
-            _lib.check(lib.nerf_train_occ_backward_bg(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, m_live,
-                                                      P(app), rows, self.grad_ptrs, P(dapp), P(self.loss_parts), P(ws),
-                                                      ws.numel(), P(al), P(bg), bg_rows, aw, P(final), s),
-                       "nerf_train_occ_backward_bg")
-            self._zero_unused_projection(rows)
-            return self.loss_parts[0] + aw * self.loss_parts[1], final
-        _lib.check(lib.nerf_train_occ_backward(P(self.packed), P(self.packedT), P(rgb_map), P(tgt), B, N, m_live,
-                                               P(app), rows, self.grad_ptrs, P(dapp), P(self.loss_buf), P(ws),
-                                               ws.numel(), s), "nerf_train_occ_backward")
-        self._zero_unused_projection(rows)
-        return self.loss_buf[0], rgb_map
+        return self._backward(main, "nerf_train_occ_backward", (P(rgb_map), P(tgt), B, N, m_live, P(app), rows), ws,
+                              app_idx, rgb_map, bgo)
 
     def _rebuild_occupancy(self):
         from .occupancy import OccupancyGrid

@@ -46,7 +46,8 @@ def error_cases(lib):
     a time.  The valid call itself is never made, and as a second guard every mutated call but the
     ones a host table refuses also carries a workspace one byte short (nerf_param_grads: no workspace
     at all), so a mutation that slipped past its check would end at the workspace check, not at a
-    launch.  Left out because they pass every check: null for the optional pointers (t_rand, u_rand,
+    launch.  (The composite stage's entry points take no workspace: there the refused check, or the
+    empty batch's return in front of the launch, is the only end.)  Left out because they pass every check: null for the optional pointers (t_rand, u_rand,
     weights_out, z_out, coarse_*, dapp); N = 4097 for nerf_mlp_forward_live (no upper bound on N);
     the f32 setting for the entries that run under both arithmetics; B == 0 for nerf_train_occ_sample
     (it then clears the caller's live count on the device); nerf_param_grads with a workspace one
@@ -164,6 +165,67 @@ def error_cases(lib):
            "save", "masks"],
           [("R = -1", dict(R=-1)), ("N = 0", dict(N=0)), ("N = 4097", dict(N=4097)), ("R = 0", dict(R=0, M_live=0)),
            ("2^32 samples", dict(R=1 << 20, N=4096))] + live, f32_only=True)
+
+    # ---- the composite stage (no workspace: a refused check or the empty batch is all that ends a call)
+    bg = [("bg_rows = 2", dict(bg_rows=2)), ("bg null with bg_rows = 1", dict(bg=None))]
+    order = ["rgb", "sigma", "z_vals", "B", "N", "rgb_map", "depth_map", "weights", "stream"]
+    base = dict(rgb=P, sigma=P, z_vals=P, B=B, N=N, rgb_map=P, depth_map=P, weights=P, stream=None)
+    required = ["rgb", "sigma", "z_vals", "rgb_map", "depth_map"]
+    sweep("nerf_composite", order, base, required, shape)
+    order = order[:-1] + ["bg", "bg_rows", "bd", "acc_map", "stream"]
+    sweep("nerf_composite_bg", order, dict(base, bg=P, bg_rows=1, bd=6.0, acc_map=P), required, shape + bg)
+    order = ["rgb", "sigma", "z_vals", "rgb_map", "target", "B", "N", "scale", "dsigma", "drgb", "sq_err", "stream"]
+    base = dict(rgb=P, sigma=P, z_vals=P, rgb_map=P, target=P, B=B, N=N, scale=0.5, dsigma=P, drgb=P, sq_err=P,
+                stream=None)
+    sweep("nerf_composite_backward", order, base,
+          ["rgb", "sigma", "z_vals", "rgb_map", "target", "dsigma", "drgb", "sq_err"], shape)
+    order = ["rgb", "sigma", "z_vals", "grad_rgb_map", "grad_depth_map", "B", "N", "dsigma", "drgb", "stream"]
+    base = dict(rgb=P, sigma=P, z_vals=P, grad_rgb_map=P, grad_depth_map=P, B=B, N=N, dsigma=P, drgb=P, stream=None)
+    required = ["rgb", "sigma", "z_vals", "dsigma", "drgb"]
+    sweep("nerf_composite_backward_grad", order, base, required, shape)
+    sweep("nerf_composite_backward_grad_acc", order[:-1] + ["g_acc", "bd", "stream"], dict(base, g_acc=P, bd=6.0),
+          required, shape)
+    order = ["rgb_c", "sigma_c", "rgb_f", "sigma_f", "src", "z_all", "grad_rgb_map", "grad_depth_map", "B", "N", "Nf",
+             "accumulate", "dsigma_c", "drgb_c", "dsigma_f", "drgb_f", "stream"]
+    base = dict(rgb_c=P, sigma_c=P, rgb_f=P, sigma_f=P, src=P, z_all=P, grad_rgb_map=P, grad_depth_map=P, B=B, N=N,
+                Nf=NF, accumulate=1, dsigma_c=P, drgb_c=P, dsigma_f=P, drgb_f=P, stream=None)
+    required = ["rgb_c", "sigma_c", "rgb_f", "sigma_f", "src", "z_all", "dsigma_c", "drgb_c", "dsigma_f", "drgb_f"]
+    merged = [("B = -1", dict(B=-1)), ("N = 0", dict(N=0)), ("N = 257", dict(N=257)), ("Nf = 0", dict(Nf=0)),
+              ("Nf = 1025", dict(Nf=1025)), ("B = 0", dict(B=0))]
+    sweep("nerf_composite_merged_backward", order, base, required, merged)
+    sweep("nerf_composite_merged_backward_acc", order[:-1] + ["g_acc", "bd", "stream"], dict(base, g_acc=P, bd=6.0),
+          required, merged)
+
+    # ---- the backward steps with a background
+    bg_loss = bg + [("acc_weight = -1", dict(acc_weight=-1.0)), ("acc_weight NaN", dict(acc_weight=float("nan")))]
+    bg_tail = ["alpha", "bg", "bg_rows", "acc_weight", "rgb_final", "stream"]
+    bg_args = dict(alpha=P, bg=P, bg_rows=1, acc_weight=0.5, rgb_final=P)
+    step = ["packed", "packedT", "rgb_map", "target", "B", "N", "app", "app_rows", "grads", "dapp", "loss", "workspace",
+            "ws_bytes"]
+    ws_bytes = lib.nerf_train_workspace_bytes(B, N)
+    base = dict(packed=P, packedT=P, rgb_map=P, target=P, B=B, N=N, app=P, app_rows=1, grads=grads, dapp=P, loss=P,
+                workspace=0x300000, ws_bytes=ws_bytes - 1, stream=None, **bg_args)
+    sweep("nerf_train_backward_bg", step + bg_tail, base, backward_ptrs,
+          shape + bg_loss + [("app_rows = 2", dict(app_rows=2)), ("gradient 3 null", dict(grads=grads_hole)),
+                             ("workspace one byte short", {}),
+                             ("no forward wrote the workspace", dict(ws_bytes=ws_bytes))])
+    ws_bytes = lib.nerf_train_occ_workspace_bytes(B, N)
+    i = step.index("app")
+    base = dict(base, M_live=5, workspace=0x400000, ws_bytes=ws_bytes - 1)
+    sweep("nerf_train_occ_backward_bg", step[:i] + ["M_live"] + step[i:] + bg_tail, base, backward_ptrs,
+          occ_step + bg_loss + [("gradient 3 null", dict(grads=grads_hole)),
+                                ("no forward with this M_live wrote the workspace", dict(ws_bytes=ws_bytes))],
+          f32_only=True)
+    ws_bytes = lib.nerf_train_hier_workspace_bytes(B, N, NF)
+    order = ["packed", "packedT", "rgb_map", "coarse_rgb", "target", "B", "N", "Nf", "coarse_weight", "app", "app_rows",
+             "grads", "dapp", "loss", "workspace", "ws_bytes"] + bg_tail[:-1] + ["coarse_final", "stream"]
+    base = dict(base, coarse_rgb=P, Nf=NF, coarse_weight=0.1, coarse_final=P, workspace=0x500000, ws_bytes=ws_bytes - 1)
+    sweep("nerf_train_hier_backward_bg", order, base, backward_ptrs + ["coarse_rgb"],
+          [("B = -1", dict(B=-1)), ("N = 1", dict(N=1)), ("N = 257", dict(N=257)), ("Nf = 0", dict(Nf=0)),
+           ("Nf = 1025", dict(Nf=1025)), ("B = 0", dict(B=0)), ("2^31 coarse samples", dict(B=1 << 23, N=256)),
+           ("app_rows = 2", dict(app_rows=2)), ("coarse_weight = -1", dict(coarse_weight=-1.0)),
+           ("gradient 3 null", dict(grads=grads_hole)), ("workspace one byte short", {}),
+           ("no forward wrote the workspace", dict(ws_bytes=ws_bytes))] + bg_loss)
     return out
 
 
@@ -197,7 +259,7 @@ def test_error_parity_with_the_recording():
     for k, (rc, msg) in want.items():
         assert rc != 2, k
         assert (rc == 0) == k.endswith((": B = 0", ": R = 0", ": M = 0")), k
-    assert len(want) >= 175
+    assert len(want) >= 327
 
 
 if __name__ == "__main__":
