@@ -6,6 +6,7 @@
 #include <utility>
 #include "../../include/nerfmi_train.h"
 #include "layout.h"
+#include "sample_index.h"
 
 namespace nerf {
 

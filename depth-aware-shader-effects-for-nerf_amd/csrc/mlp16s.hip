@@ -50,7 +50,10 @@
 // are loaded during layer 7, and its positional encoding and layer-0 operands are computed as side
 // work in the 32 segments of layer 7's group B and of the colour layer that carry no quarter.  Per
 // sample the arithmetic is the one-block kernel's, operation for operation (DESIGN §4 has the stamps
-// and the same-box A/B of each step).
+// and the same-box A/B of each step).  The loop's body holds no division (a sample's ray is a
+// multiply-high by the launcher's reciprocal of N, sample_index.h; the scales' reciprocals are exponent
+// arithmetic) and no branch ahead of the heads: a branch ends the basic block, and the compiler sinks
+// work out of the MFMA shadow into the block behind it.
 #include <atomic>
 #include "common.h"
 #include "pe_sin.h"
@@ -412,14 +415,46 @@ __device__ __forceinline__ void sgroup(const float* __restrict__ stream, int c0,
   });
 }
 
-// The sample's value over its 4 lane groups
+// A layer's tiles 4-7 stay in their accumulator registers across the layer's edge (the layer loop's
+// back edge, a peeled layer's entry): opaque there in the `a` class, each value is copied out where the
+// next layer's side work converts it.  Left to itself the compiler copies all 64 values to vector
+// registers at the edge, in one burst with the matrix pipe empty, and keeps them there.
+__device__ __forceinline__ void sacc_hold(SAcc& acc) {
+#ifndef NERF16S_EDGE_BURST   // (A/B build: the compiler's copies)
+#pragma unroll
+  for (int T = 4; T < 8; ++T)
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int st = 0; st < 2; ++st) asm volatile("" : "+a"(acc[T][r][st]));
+#endif
+}
+
+// The sample's value over its 4 lane groups.  The exchange is gfx950's row and half swaps of two
+// copies of the value (v_permlane16_swap: the first copy's odd 16-lane rows against the second's even
+// rows; v_permlane32_swap: the first's upper half against the second's lower half), after which the
+// two copies hold both partners in every lane: two VALU instructions where __shfl_xor takes a
+// ds_bpermute round trip.  smax4 sits between a layer's two groups with the matrix pipe empty, four
+// dependent round trips per layer.  max and + commute, so each lane combines the same two values as
+// with __shfl_xor(., 16) and __shfl_xor(., 32): the same bits.
+typedef unsigned u32x2s __attribute__((ext_vector_type(2)));
+template <typename F>
+__device__ __forceinline__ float sover4(float v, F&& f) {
+#ifdef NERF16S_SHFL_REDUCE   // (A/B build: the shuffles)
+  v = f(v, __shfl_xor(v, 16));
+  return f(v, __shfl_xor(v, 32));
+#else
+  const u32x2s a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  v = f(__uint_as_float(a[0]), __uint_as_float(a[1]));
+  const u32x2s b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return f(__uint_as_float(b[0]), __uint_as_float(b[1]));
+#endif
+}
 __device__ __forceinline__ float smax4(float m) {
-  m = fmaxf(m, __shfl_xor(m, 16));
-  return fmaxf(m, __shfl_xor(m, 32));
+  return sover4(m, [](float x, float y) { return fmaxf(x, y); });
 }
 __device__ __forceinline__ float ssum4(float v) {
-  v = v + __shfl_xor(v, 16);
-  return v + __shfl_xor(v, 32);
+  return sover4(v, [](float x, float y) { return x + y; });
 }
 
 struct SQuarter {
@@ -579,8 +614,9 @@ int launch_mlp16s(const float* packed, const float* o, const float* d, const flo
   const int64_t blocks = (M + per_block - 1) / per_block;
   const int cus = device_cus();
   if (cus <= 0) return set_error(NERF_ERR_HIP, "mlp16s_kernel: cannot read the device's CU count");
+  const RayDiv nd = ray_div_of(N);   // sample -> ray without a division in the kernel
   hipLaunchKernelGGL(mlp16s_kernel, dim3((unsigned)(blocks < cus ? blocks : cus)), dim3(64 * kW16Waves), 0, s, packed, o, d, z, M, N, feat,
-                     rgb, sigma, out_slot, out_T);
+                     rgb, sigma, out_slot, out_T, nd.mul, nd.shift);
   return check_launch("mlp16s_kernel");
 }
 
@@ -596,8 +632,9 @@ int launch_mlp16s_live(const float* packed, const float* o, const float* d, cons
   const int64_t blocks = (M + per_block - 1) / per_block;
   const int cus = device_cus();
   if (cus <= 0) return set_error(NERF_ERR_HIP, "mlp16s_live_kernel: cannot read the device's CU count");
+  const RayDiv nd = ray_div_of(N);
   hipLaunchKernelGGL(mlp16s_live_kernel, dim3((unsigned)(blocks < cus ? blocks : cus)), dim3(64 * kW16Waves), 0, s,
-                     packed, o, d, z, N, feat, rgb, sigma, live, live_count);
+                     packed, o, d, z, N, feat, rgb, sigma, live, live_count, nd.mul, nd.shift);
   return check_launch("mlp16s_live_kernel");
 }
 

@@ -11,11 +11,13 @@ __global__ void __launch_bounds__(64 * kW16Waves, 1)
 #if MLP16S_GATHER
 mlp16s_live_kernel(const float* __restrict__ packed, const float* __restrict__ orig, const float* __restrict__ dirs,
                    const float* __restrict__ zv, int N, const float* __restrict__ feat, float* __restrict__ rgb,
-                   float* __restrict__ sigma, const int* __restrict__ live, const int* __restrict__ live_count) {
+                   float* __restrict__ sigma, const int* __restrict__ live, const int* __restrict__ live_count,
+                   uint32_t n_mul, int n_shift) {
 #else
 mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, const float* __restrict__ dirs,
               const float* __restrict__ zv, int64_t M, int N, const float* __restrict__ feat,
-              float* __restrict__ rgb, float* __restrict__ sigma, const int* __restrict__ out_slot, int out_T) {
+              float* __restrict__ rgb, float* __restrict__ sigma, const int* __restrict__ out_slot, int out_T,
+              uint32_t n_mul, int n_shift) {
 #endif
   __shared__ __attribute__((aligned(16))) float lds[kSLdsFloats + kSStampFloats];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane0 = threadIdx.x & 63;
@@ -34,11 +36,37 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   // on blockIdx.x alone, so the four waves run the same barriers.
   const int nblk = (int)((M + 32 * kW16Waves - 1) / (32 * kW16Waves));
   int blk = blockIdx.x;
+  // (unsigned: the block one past the end may pass 2^31 before the clamp)
   auto sample_of = [&](int b, int st) {
-    return imin64(((int64_t)b * kW16Waves + wave) * 32 + 16 * st + (lane0 & 15), (int64_t)mlast);
+    const uint32_t i = ((uint32_t)b * kW16Waves + wave) * 32 + 16 * st + (lane0 & 15);
+    return (int)(i < (uint32_t)mlast ? i : (uint32_t)mlast);
   };
-  // a block's inputs as loaded (SIn) and its sample positions from them
+  // a sample's ray, sm / N: one multiply-high by the host's reciprocal of N (sample_index.h), no
+  // division in the block loop
+  auto ray_of = [&](int sm) {
+#ifdef NERF16S_DIV_INDEX   // (A/B build: the compiler's division)
+    return sm / N;
+#else
+    return ray_div(sm, n_mul, n_shift);
+#endif
+  };
+  // cst / s for a scale s of pow2_scale's: s is a power of two, the product by its exact reciprocal is
+  // the same correctly rounded value as the IEEE division's eleven instructions
+  auto over_scale = [](float c, float s) {
+#ifdef NERF16S_IEEE_INV   // (A/B build: the division)
+    return c / s;
+#else
+    return c * pow2_recip(s);
+#endif
+  };
+  // a block's inputs as loaded (SIn) and its sample positions from them.  The loads carry no branch
+  // on zv (a branch behind a publish splits the block loop's body and waits for its loads on the
+  // spot): without z values (points, row = sample) z and the directions are read from `orig`, which
+  // holds a row per sample then, and positions() drops them.
   float in_z[2], in_o[2][3], in_d[2][3];
+  const int pt_mask = zv ? 0 : -1;
+  const float* const z_or = zv ? zv : orig;
+  const float* const d_or = zv ? dirs : orig;
 #if MLP16S_GATHER
   // the block's samples (sm_cur) and the next block's (sm_n), read from the live list at the
   // positions sample_of gives
@@ -55,19 +83,14 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   auto load_inputs = [&](int b) __attribute__((always_inline)) {
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
-      const int sm = (int)sample_of(b, st);
+      const int sm = sample_of(b, st);
 #endif
-      const int64_t row = zv ? sm / N : sm;   // the sample's ray, or the point itself
+      const int64_t row = (ray_of(sm) & ~pt_mask) | (sm & pt_mask);   // the sample's ray, or the point itself
 #pragma unroll
       for (int c = 0; c < 3; ++c) in_o[st][c] = orig[3 * row + c];
-      in_z[st] = 0.0f;
+      in_z[st] = z_or[sm];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) in_d[st][c] = 0.0f;
-      if (zv) {
-        in_z[st] = zv[sm];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) in_d[st][c] = dirs[3 * row + c];
-      }
+      for (int c = 0; c < 3; ++c) in_d[st][c] = d_or[3 * row + c];
     }
   };
   float x[2][3];
@@ -77,7 +100,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
 #pragma unroll
       for (int c = 0; c < 3; ++c) {   // pts = o + d*z with separate roundings (ray_utils.py:86)
         const float p = in_o[st][c] + in_d[st][c] * in_z[st];
-        x[st][c] = zv ? p : in_o[st][c];
+        x[st][c] = pt_mask ? in_o[st][c] : p;
       }
   };
 #if MLP16S_GATHER
@@ -156,7 +179,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
 #endif
   STAMP16S(0);
   STAMP16S_REAL(12);
-  const int64_t s0 = ((int64_t)blk * kW16Waves + wave) * 32;
+  const uint32_t s0 = ((uint32_t)blk * kW16Waves + wave) * 32;
 
   // PE: lane group g = 2s + h computes slots 8 (2t + s) + j (t = 0, 1) of both its samples, sin for
   // h = 0 and cos for h = 1 (pe_feature; slot 30: x0 | x1, 31: x2 | 0).  Slot p < 30 is frequency
@@ -246,6 +269,12 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
     if constexpr (decltype(ic)::value == 2) {
 #endif
       asm volatile("" : "+v"(lane_n));
+      // (the loaded inputs opaque until here: otherwise their positions are computed, and the loads
+      // waited for, right behind the loads' issue)
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+        asm volatile("" : "+v"(in_z[st]), "+v"(in_o[st][0]), "+v"(in_o[st][1]), "+v"(in_o[st][2]), "+v"(in_d[st][0]),
+                     "+v"(in_d[st][1]), "+v"(in_d[st][2]));
       positions(xn);
 #pragma unroll
       for (int st = 0; st < 2; ++st) s_n[st] = pow2_scale(pe_bound(xn, st));
@@ -279,7 +308,7 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   Operand in[16];
 #pragma unroll
   for (int st = 0; st < 2; ++st) {
-    inv_cur[st] = cst[kS16InvW + 0] / s_cur[st];
+    inv_cur[st] = over_scale(cst[kS16InvW + 0], s_cur[st]);
     s_nxt[st] = pow2_scale(cst[kS16R + 0] * m_pe[st] + cst[kS16B + 0]);
   }
   SQuarter qv[2];
@@ -366,9 +395,10 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   auto layer = [&](int L, auto skip_tag, auto sg_tag, auto&& pub_a) __attribute__((always_inline)) {
     constexpr bool SKIP = decltype(skip_tag)::value;
     constexpr bool SG = decltype(sg_tag)::value;
+    sacc_hold(acc);
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
-      inv_cur[st] = cst[kS16InvW + L] / s_cur[st];
+      inv_cur[st] = over_scale(cst[kS16InvW + L], s_cur[st]);
       if constexpr (SKIP) s_pe[st] = s_cur[st];
     }
     const float* bias_l = bias + L * kHidden;
@@ -438,8 +468,20 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   // last block those chunks are fetched for nothing, once per workgroup).  When N is a multiple of 32
   // the wave's samples lie on one ray: its 1 KiB of ray features is DMA'd into LDS meanwhile; it is
   // older than the wrapped chunks' pieces, so the layer's publishes cover it.
+  // The DMA is issued whatever N is (a wave that spans rays reads its rows from memory below and
+  // leaves the copy unused: the row of its first sample's ray is a valid one): a branch here ends
+  // the basic block, and the compiler sinks what only the colour layer and the heads read (the density
+  // head's 64 partial products, the next block's scales) out of layer 7's MFMA shadow into the
+  // block behind it, with the registers that keeps alive saved and restored around the branch.
+#if MLP16S_GATHER
   if (one_ray) {
-    const char* src = reinterpret_cast<const char*>(feat + (imin64(s0, M - 1) / N) * kRayFeat);
+#elif defined(NERF16S_DMA_BRANCH)   // (A/B build: the DMA only when it is used)
+  if (one_ray) {
+#else
+  {
+#endif
+    const int first = (int)(s0 < (uint32_t)mlast ? s0 : (uint32_t)mlast);
+    const char* src = reinterpret_cast<const char*>(feat + (int64_t)ray_of(first) * kRayFeat);
     const uint32_t dst = (uint32_t)(uintptr_t)(lptr_t)feat_mine;
     uint32_t keep;
     asm volatile(
@@ -452,8 +494,9 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
         : "v"(16u * lane), "s"(src), "s"(dst)
         : "memory");
   }
+  sacc_hold(acc);
 #pragma unroll
-  for (int st = 0; st < 2; ++st) inv_cur[st] = cst[kS16InvW + 8] / s_cur[st];
+  for (int st = 0; st < 2; ++st) inv_cur[st] = over_scale(cst[kS16InvW + 8], s_cur[st]);
   sgroup<0, 8, 0, 3, kSPrevPe, true>(
       stream, s16_chunk0(8), lds, lds_dma, voff, off, a, acc, act_operand,
       [&](auto i, auto seg, auto ph) __attribute__((always_inline)) {
@@ -494,11 +537,11 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
     colour_head(feat_mine, 1);
   } else {
 #if MLP16S_GATHER
-    colour_head(feat + (int64_t)(sm_cur[0] / N) * kRayFeat, 0);
-    colour_head(feat + (int64_t)(sm_cur[1] / N) * kRayFeat, 1);
+    colour_head(feat + (int64_t)ray_of(sm_cur[0]) * kRayFeat, 0);
+    colour_head(feat + (int64_t)ray_of(sm_cur[1]) * kRayFeat, 1);
 #else
-    colour_head(feat + (int64_t)((int)sample_of(blk, 0) / N) * kRayFeat, 0);
-    colour_head(feat + (int64_t)((int)sample_of(blk, 1) / N) * kRayFeat, 1);
+    colour_head(feat + (int64_t)ray_of(sample_of(blk, 0)) * kRayFeat, 0);
+    colour_head(feat + (int64_t)ray_of(sample_of(blk, 1)) * kRayFeat, 1);
 #endif
   }
   // Lane group st (0, 1) writes sample tile st.  Every lane holds both tiles' sums, but evaluates the
@@ -514,13 +557,13 @@ mlp16s_kernel(const float* __restrict__ packed, const float* __restrict__ orig, 
   // lane group st writes sample tile st
   if (g < 2) {
     const int st = g;
-    if (s0 + 16 * st + li < M) {
+    if (s0 + 16 * st + li <= (uint32_t)mlast) {
 #if MLP16S_GATHER
       const int sm = st ? sm_cur[1] : sm_cur[0];
 #else
       const int sm = (int)(s0 + 16 * st + li);
 #endif
-      const int64_t o_s = out_slot ? (int64_t)(sm / N) * out_T + out_slot[sm] : (int64_t)sm;
+      const int64_t o_s = out_slot ? (int64_t)ray_of(sm) * out_T + out_slot[sm] : (int64_t)sm;
       sigma[o_s] = st ? sig[1] : sig[0];
 #pragma unroll
       for (int c = 0; c < 3; ++c) rgb[3 * o_s + c] = out[c];
