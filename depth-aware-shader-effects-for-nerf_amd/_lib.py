@@ -180,6 +180,27 @@ _SIGNATURES = {
     "nerf_composite_merged_backward_acc": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int,
                                                           ctypes.c_int, ctypes.c_int, _V, _V, _V, _V, _V,
                                                           ctypes.c_float, _V]),
+    # training with the distortion loss (include/nerfmi_train.h): the _bg entries' arguments, then dist_weight,
+    # near, far / the _acc stages' arguments, then g_w in front of the stream
+    "nerf_distortion": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                       _V, _V, _V]),
+    "nerf_train_backward_dist": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _I64,
+                                                ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V, _V,
+                                                _I64, ctypes.c_double, _V, ctypes.c_double, ctypes.c_double,
+                                                ctypes.c_double, _V]),
+    "nerf_train_occ_backward_dist": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _I64, _V, _I64,
+                                                    ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V,
+                                                    _V, _I64, ctypes.c_double, _V, ctypes.c_double, ctypes.c_double,
+                                                    ctypes.c_double, _V]),
+    "nerf_train_hier_backward_dist": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_double, _V, _I64, ctypes.POINTER(ctypes.c_void_p), _V,
+                                                     _V, _V, ctypes.c_size_t, _V, _V, _I64, ctypes.c_double, _V, _V,
+                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _V]),
+    "nerf_composite_backward_grad_w": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V,
+                                                      ctypes.c_float, _V, _V]),
+    "nerf_composite_merged_backward_w": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int,
+                                                        ctypes.c_int, ctypes.c_int, _V, _V, _V, _V, _V,
+                                                        ctypes.c_float, _V, _V]),
     # depth-aware post effects (include/nerfmi.h)
     "nerf_effect_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "nerf_depth_normalize": (ctypes.c_int, [_V, _I64, _V, _V, ctypes.c_size_t, _V]),

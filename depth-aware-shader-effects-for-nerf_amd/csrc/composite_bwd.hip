@@ -7,6 +7,8 @@
 //   composite_merged_backward_kernel   the same over the N + Nf merged samples of the hierarchical
 //                               step, gathered from and written back to the coarse and fine rows
 //                               through LDS
+// Each also in an _acc form (a per-ray upstream gradient of the opacity, a background depth: DESIGN.md §15)
+// and a _w form (the _acc form with a per-sample upstream gradient of the weights: DESIGN.md §16).
 #include "composite_plan.h"
 #include "train_internal.h"
 
@@ -45,21 +47,38 @@ namespace nerf {
 // (40 KB at its kMergedBwdMaxT).
 constexpr int kMergedBwdChunks = kMergedBwdMaxT / 64;
 
-#define COMPOSITE_BWD_ACC 0   // (the kernels, twice: composite_bwd_body.h)
+#define COMPOSITE_BWD_ACC 0   // (the kernels, three times: composite_bwd_body.h)
 #include "composite_bwd_body.h"
 #undef COMPOSITE_BWD_ACC
 #define COMPOSITE_BWD_ACC 1
 #include "composite_bwd_body.h"
+#undef COMPOSITE_BWD_W
+#define COMPOSITE_BWD_W 1
+#include "composite_bwd_body.h"
+#undef COMPOSITE_BWD_W
 #undef COMPOSITE_BWD_ACC
 
 int launch_composite_backward(const CompositeSamples& in, const CompositeUpstream& up, const CompositeAccGrad* acc,
                               const CompositeGrads& out, hipStream_t s) {
-  const CompositePlan p = composite_backward_plan(in.B, in.N, in.Nf, in.merged, acc != nullptr);
+  const bool per_sample = acc && acc->g_w;
+  const CompositePlan p = composite_backward_plan(in.B, in.N, in.Nf, in.merged, acc != nullptr, per_sample);
   if (p.action == CompositePlan::kSkip) return NERF_OK;
   if (p.action == CompositePlan::kRefuse)
     return set_error(NERF_ERR_UNSUPPORTED, "composite_merged_backward: N=%d Nf=%d (N + Nf <= %d)", in.N, in.Nf,
                      kMergedBwdMaxT);
   const dim3 grid(p.grid), block(p.block);
+  if (p.per_sample) {   // the _w kernels: the _acc arguments and g_w
+    if (p.merged)
+      hipLaunchKernelGGL(composite_merged_backward_w_kernel, grid, block, p.lds, s, in.rgb, in.sigma, in.rgb_f,
+                         in.sigma_f, in.src, in.z, up.rgb_map, up.target, up.grad_map, up.grad_depth, in.B, in.N, in.Nf,
+                         up.scale, out.accumulate, out.dsigma, out.drgb, out.dsigma_f, out.drgb_f, up.sq_err, acc->g_acc,
+                         acc->bd, acc->g_w);
+    else
+      hipLaunchKernelGGL(composite_backward_w_kernel, grid, block, p.lds, s, in.rgb, in.sigma, in.z, up.rgb_map,
+                         up.target, up.grad_map, up.grad_depth, in.B, in.N, up.scale, out.dsigma, out.drgb, up.sq_err,
+                         acc->g_acc, acc->bd, acc->g_w);
+    return check_launch(p.name);
+  }
   switch (p.merged << 1 | p.alt) {
     case 0:
       hipLaunchKernelGGL(composite_backward_kernel, grid, block, p.lds, s, in.rgb, in.sigma, in.z, up.rgb_map, up.target,

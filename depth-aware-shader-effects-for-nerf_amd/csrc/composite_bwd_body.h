@@ -6,8 +6,22 @@
 //     bd is not NaN the depth is S + k bd, k = max(0, 1 - acc), and its term is gd (z_s - bd) where
 //     k > 0 and gd z_s where k == 0.  Same arithmetic order: double scans, d sigma rounded once.  With
 //     g_acc null or zero and bd NaN every operation is the plain kernel's: the same bits.
+//   COMPOSITE_BWD_ACC 1 with COMPOSITE_BWD_W 1: composite_backward_w_kernel and
+//     composite_merged_backward_w_kernel, the _acc text with a per-sample upstream gradient g_w of the
+//     weights ((B,N); merged: (B,N+Nf) in merged order; nullable = 0), added to the sample's dw right
+//     after g_acc.  With g_w null or zero every operation is the _acc kernel's.
+#ifndef COMPOSITE_BWD_W
+#define COMPOSITE_BWD_W 0
+#endif
 __global__ void __launch_bounds__(256)
-#if COMPOSITE_BWD_ACC
+#if COMPOSITE_BWD_W
+composite_backward_w_kernel(const float* __restrict__ rgb, const float* __restrict__ sigma,
+                            const float* __restrict__ zv, const float* __restrict__ rgb_map,
+                            const float* __restrict__ target, const float* __restrict__ grad_map,
+                            const float* __restrict__ grad_depth, int64_t B, int N, float scale,
+                            float* __restrict__ dsigma, float* __restrict__ drgb, float* __restrict__ sq_err,
+                            const float* __restrict__ g_acc, float bd, const float* __restrict__ g_w) {
+#elif COMPOSITE_BWD_ACC
 composite_backward_acc_kernel(const float* __restrict__ rgb, const float* __restrict__ sigma,
                               const float* __restrict__ zv, const float* __restrict__ rgb_map,
                               const float* __restrict__ target, const float* __restrict__ grad_map,
@@ -147,6 +161,10 @@ composite_backward_kernel(const float* __restrict__ rgb, const float* __restrict
 #if COMPOSITE_BWD_ACC
       if (ga != 0.0f) dw += (double)ga;
 #endif
+#if COMPOSITE_BWD_W
+      const float gw = g_w ? g_w[base + s] : 0.0f;   // d loss / d w_s from outside the composite
+      if (gw != 0.0f) dw += (double)gw;
+#endif
     }
     // exclusive suffix sum of dw*w inside the chunk, plus the chunks after it
     double v = valid ? dw * ((double)alpha * T) : 0.0;
@@ -166,7 +184,9 @@ composite_backward_kernel(const float* __restrict__ rgb, const float* __restrict
 }
 
 __global__ void __launch_bounds__(256)
-#if COMPOSITE_BWD_ACC
+#if COMPOSITE_BWD_W
+composite_merged_backward_w_kernel(
+#elif COMPOSITE_BWD_ACC
 composite_merged_backward_acc_kernel(
 #else
 composite_merged_backward_kernel(
@@ -181,6 +201,9 @@ composite_merged_backward_kernel(
                                  float* __restrict__ sq_err
 #if COMPOSITE_BWD_ACC
                                  , const float* __restrict__ g_acc, float bd
+#endif
+#if COMPOSITE_BWD_W
+                                 , const float* __restrict__ g_w
 #endif
                                  ) {
   extern __shared__ f32x4 quads[];    // [rays per block][T]
@@ -313,6 +336,10 @@ composite_merged_backward_kernel(
       if (gd != 0.0f) dw += (double)gd * ((double)z - dmean) * dinv;
 #if COMPOSITE_BWD_ACC
       if (ga != 0.0f) dw += (double)ga;
+#endif
+#if COMPOSITE_BWD_W
+      const float gw = g_w ? g_w[base + s] : 0.0f;   // d loss / d w_s from outside the composite
+      if (gw != 0.0f) dw += (double)gw;
 #endif
     }
     double v = valid ? dw * ((double)alpha * Tr) : 0.0;

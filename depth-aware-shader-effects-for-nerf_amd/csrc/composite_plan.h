@@ -20,6 +20,7 @@ struct CompositePlan {
   unsigned grid, block;
   size_t lds;                // dynamic LDS bytes
   const char* name;          // what check_launch reports
+  bool per_sample;           // backward: the _w kernels (alt is set too)
 };
 
 inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
@@ -45,11 +46,14 @@ inline CompositePlan composite_forward_plan(int64_t B, int N, int Nf, bool merge
 
 // Backward: one wave per ray.  The merged kernel keeps a ray's T = N + Nf quads in LDS: 4 rays per
 // block up to T = 768 and 2 beyond (40 KB at kMergedBwdMaxT).
-inline CompositePlan composite_backward_plan(int64_t B, int N, int Nf, bool merged, bool acc) {
+// per_sample (with acc): the _w kernels, the _acc ones with a per-sample gradient of the weights; the
+// same grid, block and LDS.
+inline CompositePlan composite_backward_plan(int64_t B, int N, int Nf, bool merged, bool acc, bool per_sample = false) {
   CompositePlan p{};
-  p.merged = merged, p.alt = acc;
+  p.merged = merged, p.alt = acc, p.per_sample = acc && per_sample;
   p.name = merged ? (acc ? "composite_merged_backward_acc_kernel" : "composite_merged_backward_kernel")
                   : (acc ? "composite_backward_acc_kernel" : "composite_backward_kernel");
+  if (p.per_sample) p.name = merged ? "composite_merged_backward_w_kernel" : "composite_backward_w_kernel";
   if (B == 0) return p;
   const int T = N + Nf;
   if (merged && (N < 1 || Nf < 1 || T > kMergedBwdMaxT)) {

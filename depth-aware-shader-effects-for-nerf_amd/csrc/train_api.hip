@@ -214,25 +214,70 @@ static BgScratch bg_scratch(float* grad_rows, int64_t B) {
 }
 static_assert(kGradRow >= 6 * 64, "the head's per-ray scratch fits in a ray's gradient rows");
 
+// ---- the distortion term (include/nerfmi_train.h "distortion")
+// The _dist entries' addition to the head above.  Off (weight 0): the _bg entry's calls.
+struct DistLoss {
+  double weight, near, far;
+  bool off() const { return weight == 0.0; }
+};
+
+static int check_dist_loss(const char* fn, const DistLoss& d) {
+  REQUIRE(d.weight >= 0.0 && d.weight <= 3.0e38, "%s: dist_weight=%g (>= 0)", fn, d.weight);   // (NaN fails)
+  REQUIRE(d.off() || (d.far > d.near && d.far - d.near <= 1.7e308 && d.near >= -1.7e308),
+          "%s: near=%g far=%g (finite, far > near) with dist_weight > 0", fn, d.near, d.far);
+  return NERF_OK;
+}
+
+// Its scratch, behind the head's in the same gradient rows: the composite's weights (B,T), their gradient
+// g_w (B,T) and the per-ray loss (B), each at a 64-float boundary.  `rows` is the number of samples whose
+// gradient rows the set owns (whole 32-row tiles of kGradRow floats); null when that is too small.
+struct DistScratch {
+  float *weights, *g_w, *loss_rays;
+};
+static bool dist_scratch(float* grad_rows, int64_t rows, int64_t B, int T, DistScratch& t) {
+  const size_t b = ((size_t)B + 63) & ~(size_t)63, bt = ((size_t)B * (size_t)T + 63) & ~(size_t)63;
+  t.weights = grad_rows + 6 * b;
+  t.g_w = t.weights + bt;
+  t.loss_rays = t.g_w + bt;
+  return 7 * b + 2 * bt <= (size_t)tile_rows(rows) * kGradRow;
+}
+
 // The head of sample set `in` (its per-ray regions are w's) from its per-ray gradient (g_rgb, g_acc), and
 // the two means: the composite once more for the opacity of the rows the forward left (its maps go to the
 // set's unused `maps` region), the per-ray loss, the composite backward in its _acc form into `out`.
+// With a distortion term (d non-null and on; `rows` = the samples of w's gradient rows) the composite
+// also leaves its weights in the scratch, distortion_kernel turns them into the per-ray loss and
+// g_w = weight d.weight / B * dl/dw, and the backward runs in its _w form with (g_rgb, g_acc, g_w).
 static int backward_head_bg(const TrainWs& w, const CompositeSamples& in, const CompositeGrads& out,
                             const float* rgb_map, const float* target, const BgLoss& o, double weight, float* loss_rgb,
-                            float* loss_acc, float* rgb_final, hipStream_t s) {
+                            float* loss_acc, float* rgb_final, hipStream_t s, const DistLoss* d = nullptr,
+                            int64_t rows = 0, float* loss_dist = nullptr) {
   const int64_t B = in.B;
   const BgScratch t = bg_scratch(w.grad, B);
   const CompositeBg acc_only{nullptr, 0, __builtin_nanf(""), t.acc};
-  const CompositeAccGrad acc{t.g_acc, __builtin_nanf("")};
+  CompositeAccGrad acc{t.g_acc, __builtin_nanf("")};
+  const bool dist = d && !d->off();
+  DistScratch ds{};
+  const int T = in.merged ? in.N + in.Nf : in.N;
+  if (dist && !dist_scratch(w.grad, rows, B, T, ds))
+    return set_error(NERF_ERR_WORKSPACE, "distortion: the scratch of B=%lld T=%d exceeds the gradient rows",
+                     (long long)B, T);
   int rc;
-  if ((rc = launch_composite(in, w.maps, w.maps + 3 * B, nullptr, &acc_only, s))) return rc;
+  if ((rc = launch_composite(in, w.maps, w.maps + 3 * B, ds.weights, &acc_only, s))) return rc;
+  if (dist) {
+    if ((rc = launch_distortion(ds.weights, in.z, B, T, 1.0 / (d->far - d->near), weight * d->weight / (double)B,
+                                ds.loss_rays, ds.g_w, s)))
+      return rc;
+    acc.g_w = ds.g_w;
+  }
   if ((rc = launch_bg_loss(rgb_map, t.acc, target, o.alpha, o.bg_rows ? o.bg : nullptr, o.bg_rows > 1 ? 3 : 0,
                            (float)o.acc_weight, (float)(weight * 2.0 / (3.0 * (double)B)),
                            (float)(weight * 2.0 / (double)B), B, t.g_rgb, t.g_acc, w.sq_err, t.sq_acc, rgb_final, s)))
     return rc;
   if ((rc = launch_composite_backward(in, upstream_grad(t.g_rgb, nullptr), &acc, out, s))) return rc;
   if ((rc = launch_loss(w.sq_err, B, loss_rgb, s))) return rc;
-  return launch_loss_rays(t.sq_acc, B, loss_acc, s);
+  if ((rc = launch_loss_rays(t.sq_acc, B, loss_acc, s))) return rc;
+  return dist ? launch_loss_rays(ds.loss_rays, B, loss_dist, s) : NERF_OK;
 }
 }  // namespace nerf
 
@@ -615,8 +660,14 @@ static int bg_off_outputs(const char* fn, float* loss_acc, int n_acc, float* rgb
 
 // The head of the dense step and, on its zero-filled dense rows (a dead sample has weight 0), of the
 // occupancy step; bgl null: the entry without a background.
+// dl null: no distortion entry; off: its float (loss[2]) reads 0 after the _bg entry's calls.
 static int dense_head(const char* fn, const TrainWs& w, const float* rgb_map, const float* target, int64_t B, int N,
-                      const BgLoss* bgl, float* loss, float* rgb_final, hipStream_t s) {
+                      const BgLoss* bgl, float* loss, float* rgb_final, hipStream_t s, const DistLoss* dl = nullptr) {
+  if (dl && !dl->off())
+    return backward_head_bg(w, w.samples(B, N), w.grads(), rgb_map, target, *bgl, 1.0, loss, loss + 1, rgb_final, s, dl,
+                            B * N, loss + 2);
+  if (dl && hipMemsetAsync(loss + 2, 0, 4, s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
   if (bgl && !bgl->off())
     return backward_head_bg(w, w.samples(B, N), w.grads(), rgb_map, target, *bgl, 1.0, loss, loss + 1, rgb_final, s);
   if (int rc = backward_head(w, rgb_map, target, B, N, loss, s)) return rc;
@@ -667,11 +718,12 @@ int nerf_train_forward(const float* packed, const float* rays_o, const float* ra
 static int train_backward(const char* fn, const float* packed, const float* packedT, const float* rgb_map,
                           const float* target, int64_t B, int N, const float* app, int64_t app_rows,
                           float* const* param_grads_out, float* dapp, float* loss, void* workspace, size_t ws_bytes,
-                          const BgLoss* bgl, float* rgb_final, nerf_stream_t stream) {
+                          const BgLoss* bgl, float* rgb_final, nerf_stream_t stream, const DistLoss* dl = nullptr) {
   REQUIRE(B >= 0 && N >= 1 && N <= 4096, "%s: B=%lld N=%d", fn, (long long)B, N);
   REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "%s: app_rows=%lld", fn, (long long)app_rows);
   int rc;
   if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
+  if (dl && (rc = check_dist_loss(fn, *dl))) return rc;
   if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
                                 workspace)))
     return rc;
@@ -687,7 +739,7 @@ static int train_backward(const char* fn, const float* packed, const float* pack
     return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_forward wrote this workspace", fn);
   const uint32_t* masks = fwd.arith == NERF_ARITH_F16X3 ? w.masks : nullptr;
   const int64_t M = B * N;
-  if ((rc = dense_head(fn, w, rgb_map, target, B, N, bgl, loss, rgb_final, s))) return rc;
+  if ((rc = dense_head(fn, w, rgb_map, target, B, N, bgl, loss, rgb_final, s, dl))) return rc;
   if ((rc = launch_mlp_backward(packed, packedT, w.save, masks, w.sigma, w.rgb, w.dsigma, w.drgb, M, w.grad, s,
                                 /*store_dhd=*/!fused_ray_sums(N))))
     return rc;
@@ -709,6 +761,17 @@ int nerf_train_backward_bg(const float* packed, const float* packedT, const floa
   const BgLoss o{alpha, bg, bg_rows, acc_weight};
   return train_backward("nerf_train_backward_bg", packed, packedT, rgb_map, target, B, N, app, app_rows,
                         param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream);
+}
+
+int nerf_train_backward_dist(const float* packed, const float* packedT, const float* rgb_map, const float* target,
+                             int64_t B, int N, const float* app, int64_t app_rows, float* const* param_grads_out,
+                             float* dapp, float* loss, void* workspace, size_t ws_bytes, const float* alpha,
+                             const float* bg, int64_t bg_rows, double acc_weight, float* rgb_final, double dist_weight,
+                             double near, double far, nerf_stream_t stream) {
+  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  const DistLoss d{dist_weight, near, far};
+  return train_backward("nerf_train_backward_dist", packed, packedT, rgb_map, target, B, N, app, app_rows,
+                        param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream, &d);
 }
 
 int nerf_train_occ_sample(const float* rays_o, const float* rays_d, int64_t B, double near, double far, int N,
@@ -756,10 +819,11 @@ static int train_occ_backward(const char* fn, const float* packed, const float* 
                               const float* target, int64_t B, int N, int64_t M_live, const float* app,
                               int64_t app_rows, float* const* param_grads_out, float* dapp, float* loss,
                               void* workspace, size_t ws_bytes, const BgLoss* bgl, float* rgb_final,
-                              nerf_stream_t stream) {
+                              nerf_stream_t stream, const DistLoss* dl = nullptr) {
   int rc;
   if ((rc = check_occ_step(fn, "step", B, N, M_live, app_rows))) return rc;
   if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
+  if (dl && (rc = check_dist_loss(fn, *dl))) return rc;
   if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
                                 workspace)))
     return rc;
@@ -771,7 +835,7 @@ static int train_occ_backward(const char* fn, const float* packed, const float* 
     return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_occ_forward with M_live=%lld wrote this "
                      "workspace", fn, (long long)M_live);
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = dense_head(fn, w, rgb_map, target, B, N, bgl, loss, rgb_final, s))) return rc;
+  if ((rc = dense_head(fn, w, rgb_map, target, B, N, bgl, loss, rgb_final, s, dl))) return rc;
   if (M_live == 0) {   // every sample dead: sigma = 0 is a constant of the step, every gradient is zero
     for (int p = 0; p < P_COUNT; ++p)
       if (hipMemsetAsync(param_grads_out[p], 0, param_floats(p) * 4, s) != hipSuccess)
@@ -804,6 +868,18 @@ int nerf_train_occ_backward_bg(const float* packed, const float* packedT, const 
   const BgLoss o{alpha, bg, bg_rows, acc_weight};
   return train_occ_backward("nerf_train_occ_backward_bg", packed, packedT, rgb_map, target, B, N, M_live, app, app_rows,
                             param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream);
+}
+
+int nerf_train_occ_backward_dist(const float* packed, const float* packedT, const float* rgb_map, const float* target,
+                                 int64_t B, int N, int64_t M_live, const float* app, int64_t app_rows,
+                                 float* const* param_grads_out, float* dapp, float* loss, void* workspace,
+                                 size_t ws_bytes, const float* alpha, const float* bg, int64_t bg_rows,
+                                 double acc_weight, float* rgb_final, double dist_weight, double near, double far,
+                                 nerf_stream_t stream) {
+  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  const DistLoss d{dist_weight, near, far};
+  return train_occ_backward("nerf_train_occ_backward_dist", packed, packedT, rgb_map, target, B, N, M_live, app,
+                            app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream, &d);
 }
 
 // ------------------------------------------------------------- the hierarchical step
@@ -874,10 +950,11 @@ static int train_hier_backward(const char* fn, const float* packed, const float*
                                double coarse_weight, const float* app, int64_t app_rows,
                                float* const* param_grads_out, float* dapp, float* loss, void* workspace,
                                size_t ws_bytes, const BgLoss* bgl, float* rgb_final, float* coarse_final,
-                               nerf_stream_t stream) {
+                               nerf_stream_t stream, const DistLoss* dl = nullptr) {
   int rc;
   if ((rc = check_hier_shape(fn, B, N, Nf))) return rc;
   if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
+  if (dl && (rc = check_dist_loss(fn, *dl))) return rc;
   REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "%s: app_rows=%lld", fn, (long long)app_rows);
   REQUIRE(coarse_weight >= 0.0 && coarse_weight <= 3.0e38, "%s: coarse_weight=%g", fn, coarse_weight);
   if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
@@ -895,7 +972,18 @@ static int train_hier_backward(const char* fn, const float* packed, const float*
   const bool f16 = fwd.arith == NERF_ARITH_F16X3;
   const double mse_scale = 2.0 / (3.0 * (double)B);
   // the coarse composite's term, then the merged composite's on top of it in the coarse rows
-  if (bgl && !bgl->off()) {
+  const bool dist = dl && !dl->off();   // off: the _bg entry's calls, and the two distortion floats read 0
+  if (dl && !dist && hipMemsetAsync(loss + 4, 0, 8, s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
+  if (dist) {
+    // the _bg heads with the distortion term of each part: loss + 4 fine, loss + 5 coarse
+    if ((rc = backward_head_bg(c, c.samples(B, N), c.grads(), coarse_rgb, target, *bgl, coarse_weight, loss + 1,
+                               loss + 3, coarse_final, s, dl, B * N, loss + 5)))
+      return rc;
+    if ((rc = backward_head_bg(f, h.merged(B, N, Nf), h.merged_grads(), rgb_map, target, *bgl, 1.0, loss, loss + 2,
+                               rgb_final, s, dl, B * Nf, loss + 4)))
+      return rc;
+  } else if (bgl && !bgl->off()) {
     // the same two terms from each part's per-ray head (the coarse part's scaled by coarse_weight); loss:
     // fine colour, coarse colour, fine opacity, coarse opacity
     if ((rc = backward_head_bg(c, c.samples(B, N), c.grads(), coarse_rgb, target, *bgl, coarse_weight, loss + 1,
@@ -971,6 +1059,57 @@ int nerf_train_hier_backward_bg(const float* packed, const float* packedT, const
   return train_hier_backward("nerf_train_hier_backward_bg", packed, packedT, rgb_map, coarse_rgb, target, B, N, Nf,
                              coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, &o,
                              rgb_final, coarse_final, stream);
+}
+
+int nerf_train_hier_backward_dist(const float* packed, const float* packedT, const float* rgb_map,
+                                  const float* coarse_rgb, const float* target, int64_t B, int N, int Nf,
+                                  double coarse_weight, const float* app, int64_t app_rows,
+                                  float* const* param_grads_out, float* dapp, float* loss, void* workspace,
+                                  size_t ws_bytes, const float* alpha, const float* bg, int64_t bg_rows,
+                                  double acc_weight, float* rgb_final, float* coarse_final, double dist_weight,
+                                  double near, double far, nerf_stream_t stream) {
+  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  const DistLoss d{dist_weight, near, far};
+  return train_hier_backward("nerf_train_hier_backward_dist", packed, packedT, rgb_map, coarse_rgb, target, B, N, Nf,
+                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, &o,
+                             rgb_final, coarse_final, stream, &d);
+}
+
+int nerf_distortion(const float* weights, const float* z_vals, int64_t B, int T, double near, double far, double scale,
+                    float* loss_rays, float* g_w, nerf_stream_t stream) {
+  REQUIRE(B >= 0, "nerf_distortion: B=%lld", (long long)B);
+  if (T < 1 || T > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_distortion: T=%d (1..4096)", T);
+  REQUIRE(far > near && far - near <= 1.7e308, "nerf_distortion: near=%g far=%g (finite, far > near)", near, far);
+  REQUIRE(scale == scale && scale >= -1.7e308 && scale <= 1.7e308, "nerf_distortion: scale=%g", scale);
+  REQUIRE(B == 0 || (weights && z_vals), "nerf_distortion: null pointer");
+  return launch_distortion(weights, z_vals, B, T, 1.0 / (far - near), scale, loss_rays, g_w, (hipStream_t)stream);
+}
+
+int nerf_composite_backward_grad_w(const float* rgb, const float* sigma, const float* z_vals, const float* grad_rgb_map,
+                                   const float* grad_depth_map, int64_t B, int N, float* dsigma, float* drgb,
+                                   const float* g_acc, float bd, const float* g_w, nerf_stream_t stream) {
+  REQUIRE(B >= 0, "nerf_composite_backward_grad_w: B=%lld", (long long)B);
+  if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward_grad_w: N=%d (1..4096)", N);
+  REQUIRE(B == 0 || (rgb && sigma && z_vals && dsigma && drgb), "nerf_composite_backward_grad_w: null pointer");
+  const CompositeAccGrad acc{g_acc, bd, g_w};
+  return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_grad(grad_rgb_map, grad_depth_map),
+                                   &acc, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
+}
+
+int nerf_composite_merged_backward_w(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
+                                     const uint16_t* src, const float* z_all, const float* grad_rgb_map,
+                                     const float* grad_depth_map, int64_t B, int N, int Nf, int accumulate_coarse,
+                                     float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f, const float* g_acc,
+                                     float bd, const float* g_w, nerf_stream_t stream) {
+  REQUIRE(B >= 0, "nerf_composite_merged_backward_w: B=%lld", (long long)B);
+  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
+    return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_merged_backward_w: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
+  REQUIRE(B == 0 || (rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c && drgb_c && dsigma_f && drgb_f),
+          "nerf_composite_merged_backward_w: null pointer");
+  const CompositeAccGrad acc{g_acc, bd, g_w};
+  return launch_composite_backward(merged_samples(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, B, N, Nf),
+                                   upstream_grad(grad_rgb_map, grad_depth_map), &acc,
+                                   {dsigma_c, drgb_c, dsigma_f, drgb_f, accumulate_coarse}, (hipStream_t)stream);
 }
 
 int nerf_composite_backward_grad_acc(const float* rgb, const float* sigma, const float* z_vals,

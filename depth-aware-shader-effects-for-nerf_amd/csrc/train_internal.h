@@ -83,9 +83,12 @@ inline CompositeUpstream upstream_grad(const float* grad_map, const float* grad_
 }
 // The opacity part (the _acc kernels: composite_bwd_body.h): g_acc (B, nullable = 0) is added
 // to every dw of the ray; bd is the forward's background depth (NaN: the normalised depth).
+// g_w ((B,N); merged: (B,N+Nf) in merged order; null: absent) is a per-sample gradient of the weights
+// themselves, added to the sample's dw: non-null selects the _w kernels.
 struct CompositeAccGrad {
   const float* g_acc;
   float bd;
+  const float* g_w = nullptr;
 };
 // d loss / d(sigma, rgb) per sample; a merged set also has the fine pair, and its coarse rows take
 // in + term when `accumulate` is set
@@ -93,9 +96,15 @@ struct CompositeGrads {
   float *dsigma, *drgb, *dsigma_f, *drgb_f;
   int accumulate;
 };
-// acc null: the plain kernels, else the _acc ones (with the gradient form of `up`)
+// acc null: the plain kernels, else the _acc ones (with the gradient form of `up`), or the _w ones when
+// acc->g_w is set
 int launch_composite_backward(const CompositeSamples& in, const CompositeUpstream& up, const CompositeAccGrad* acc,
                               const CompositeGrads& out, hipStream_t s);
+// distortion.hip: the distortion loss of the ray weights (include/nerfmi_train.h "distortion")
+// over (B,T) weights and z, T in 1..4096: loss_rays (B) = (float)l_r and g_w (B,T) = (float)(scale dl_r/dw),
+// each nullable; inv = 1 / (far - near)
+int launch_distortion(const float* weights, const float* z, int64_t B, int T, double inv, double scale,
+                      float* loss_rays, float* g_w, hipStream_t s);
 
 // the per-ray loss head of a step with a background (composite_bwd.hip; the means: launch_loss / launch_loss_rays)
 int launch_bg_loss(const float* rgb_map, const float* acc, const float* target, const float* alpha, const float* bg,

@@ -78,14 +78,23 @@ class Trainer:
     opacity, coarse opacity).  ``acc_weight`` > 0 works without a background too (black); a trainer with
     neither refuses an ``alpha`` (ValueError), so ``loss_parts`` is allocated once, by configuration.  The
     forwards are unchanged; it works dense, with ``occupancy`` and with
-    ``hierarchical``."""
+    ``hierarchical``.
+
+    ``distortion_weight``: 0 (default: the step makes the calls it makes without the argument) or a finite
+    weight > 0 of mip-NeRF 360's distortion loss on the ray weights over the trainer's near / far (the
+    _dist backwards of include/nerfmi_train.h): total = (colour + ``acc_weight`` * opacity)
+    + ``distortion_weight`` * distortion per part.  ``self.loss_parts`` is then (colour, opacity,
+    distortion), or with ``hierarchical`` (fine colour, coarse colour, fine opacity, coarse opacity, fine
+    distortion, coarse distortion).  It works dense, with ``occupancy`` and with ``hierarchical``, with or
+    without a background."""
 
     def __init__(self, config, model=None, appearance_embeddings=None, n_images=None, group=None,
                  lr=None, betas=(0.9, 0.999), eps=1e-8, near=None, far=None, occupancy=None,
                  occupancy_refresh=None, hierarchical=False, n_importance=None, coarse_loss_weight=1.0,
-                 background=None, acc_weight=0.0):
+                 background=None, acc_weight=0.0, distortion_weight=0.0):
         _check_occupancy_args(occupancy, occupancy_refresh)
         self.background, self.acc_weight = _check_background_args(background, acc_weight)
+        self.distortion_weight = _check_distortion_weight(distortion_weight)
         self.hierarchical, self.n_importance, self.coarse_loss_weight = _check_hierarchical_args(
             config, hierarchical, n_importance, coarse_loss_weight, occupancy)
         self.config = config
@@ -162,10 +171,13 @@ class Trainer:
         self._bg_row = None        # the fixed background colour as a (1,3) device tensor
         if self.hierarchical:
             # (fine, coarse) mean squared errors; with a background (fine colour, coarse colour, fine
-            # opacity, coarse opacity)
-            self._loss4 = torch.zeros(4, device=self.dev)
-            self.loss_parts = self._loss4 if self._bg_configured() else self._loss4[:2]
+            # opacity, coarse opacity), with a distortion weight also (fine distortion, coarse distortion)
+            dist = self.distortion_weight > 0.0
+            self._loss4 = torch.zeros(6 if dist else 4, device=self.dev)
+            self.loss_parts = self._loss4 if (dist or self._bg_configured()) else self._loss4[:2]
             self._ws_hier = None
+        elif self.distortion_weight > 0.0:
+            self.loss_parts = torch.zeros(3, device=self.dev)   # (colour, opacity, distortion)
         elif self._bg_configured():
             self.loss_parts = torch.zeros(2, device=self.dev)   # (colour, opacity)
         self.occupancy = occupancy
@@ -235,10 +247,13 @@ class Trainer:
 
     def _bg_args(self, B, seed, alpha):
         """None for a trainer without a background or an opacity term (the original calls; an alpha is
-        refused there); else the _bg backward's (alpha, bg, bg_rows, acc_weight, rgb_final)."""
+        refused there); else the _bg backward's (alpha, bg, bg_rows, acc_weight, rgb_final).  A trainer with
+        only a distortion weight gets them with every option off."""
         if not self._bg_configured():
             if alpha is not None:
                 raise ValueError("Trainer: alpha belongs to a trainer with background= or acc_weight > 0")
+            if self.distortion_weight > 0.0:
+                return None, None, 0, 0.0, torch.empty(B, 3, device=self.dev)
             return None
         if alpha is not None:
             alpha = alpha.reshape(-1).to(self.dev, torch.float32).contiguous()
@@ -275,7 +290,8 @@ class Trainer:
     def _backward(self, main, entry, args, ws, app_idx, rgb_map, bgo, hier=False):
         """The step variants' epilogue: the join with the transposed packing, then the C entry `entry`
         (`args`: what it takes between packedT and the gradient pointers, ending in app, rows) or, for a
-        trainer with a background, its _bg twin with `bgo` appended.  (loss, the map the loss was taken on)"""
+        trainer with a background, its _bg twin with `bgo` appended; with a distortion weight its _dist twin
+        with the weight, near and far behind those.  (loss, the map the loss was taken on)"""
         P, rows = _lib.ptr, args[-1]
         # d app of the batch's image goes straight into its row of the table's gradient
         dapp = self.app_grad[int(app_idx)] if rows else None
@@ -285,17 +301,25 @@ class Trainer:
             tail, out = (), rgb_map
         else:
             al, bg, bg_rows, aw, out = bgo
-            entry, lp = entry + "_bg", self.loss_parts
+            dw = self.distortion_weight
+            entry, lp = entry + ("_dist" if dw > 0.0 else "_bg"), self.loss_parts
             tail = (P(al), P(bg), bg_rows, aw, P(out)) + ((None,) if hier else ())     # (no coarse_final)
+            if dw > 0.0:
+                tail += (dw, self.near, self.far)
         _lib.check(getattr(self.lib, entry)(P(self.packed), P(self.packedT), *args, self.grad_ptrs, P(dapp), P(lp),
                                             P(ws), ws.numel(), *tail, _lib.stream()), entry)
         self._zero_unused_projection(rows)
         # loss_parts: (colour, opacity), hierarchical (fine colour, coarse colour, fine opacity, coarse opacity)
         if bgo is None:
             return (lp[0] + self.coarse_loss_weight * lp[1] if hier else lp[0]), out
+        # ... then with a distortion weight the distortion part(s): total = (colour + aw opacity) + dw distortion
         if hier:
-            return (lp[0] + aw * lp[2]) + self.coarse_loss_weight * (lp[1] + aw * lp[3]), out
-        return lp[0] + aw * lp[1], out
+            fine, coarse = lp[0] + aw * lp[2], lp[1] + aw * lp[3]
+            if dw > 0.0:
+                fine, coarse = fine + dw * lp[4], coarse + dw * lp[5]
+            return fine + self.coarse_loss_weight * coarse, out
+        total = lp[0] + aw * lp[1]
+        return (total + dw * lp[2] if dw > 0.0 else total), out
 
     # ------------------------------------------------------------------------------ one step
     def forward_backward(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, u_rand=None, seed=None,
@@ -594,6 +618,14 @@ def _check_background_args(background, acc_weight):
     return bg, aw
 
 
+def _check_distortion_weight(distortion_weight):
+    """The distortion loss's weight checked as acc_weight is: a finite float >= 0; ValueError otherwise."""
+    dw = float(distortion_weight)
+    if not (dw >= 0.0 and math.isfinite(dw)):
+        raise ValueError(f"Trainer: distortion_weight must be finite and >= 0, got {distortion_weight!r}")
+    return dw
+
+
 _BACKGROUND_KEY = 0xBAC6C0105EED        # the random backgrounds' stream: the step's seed ^ this
 
 
@@ -641,7 +673,7 @@ def average_gradients(flat_grad, group):
 def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iterations=None, log_every=10,
                checkpoint_every=1000, seed=None, plots=True, return_metrics=False, occupancy=None,
                occupancy_refresh=None, hierarchical=False, n_importance=None, coarse_loss_weight=1.0,
-               background=None, acc_weight=0.0, trainer_cls=None):
+               background=None, acc_weight=0.0, distortion_weight=0.0, trainer_cls=None):
     """src/train.py:13-207 on nerfmi: returns the trained model, as the reference does
     (train.py:207; run.py:347 assigns it).  ``return_metrics=True`` returns (model, losses, psnrs)
     instead; the per-iteration losses and PSNRs are also left on ``train_nerf.losses`` /
@@ -657,10 +689,12 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
     ``acc_weight`` go to the Trainer as well: with a background or an opacity weight set every step gets the
     batch's alpha channel (``batch["alpha"]``; None, the custom format, means ones), the logged loss and PSNR are the
     colour term's, and the validation render composites over the trainer's colour (white for "random").
-    ``trainer_cls`` (tests): the class constructed instead of Trainer."""
+    ``distortion_weight`` > 0 goes to the Trainer too (the distortion loss on the ray weights); the logged loss
+    and PSNR stay the colour term's.  ``trainer_cls`` (tests): the class constructed instead of Trainer."""
     import torch.distributed as dist
     _check_occupancy_args(occupancy, occupancy_refresh)
     _check_background_args(background, acc_weight)
+    dist_kwargs = {"distortion_weight": distortion_weight} if _check_distortion_weight(distortion_weight) > 0.0 else {}
     _check_hierarchical_args(config, hierarchical, n_importance, coarse_loss_weight, occupancy)
     rank = dist.get_rank(group) if group is not None else 0
     if rank == 0:
@@ -673,7 +707,7 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
         config, appearance_embeddings=getattr(dataset, "appearance_embeddings", None), n_images=len(dataset),
         group=group, near=getattr(dataset, "near", None), far=getattr(dataset, "far", None), occupancy=occupancy,
         occupancy_refresh=occupancy_refresh, hierarchical=hierarchical, n_importance=n_importance,
-        coarse_loss_weight=coarse_loss_weight, **bg_kwargs)
+        coarse_loss_weight=coarse_loss_weight, **bg_kwargs, **dist_kwargs)
     iters = config.num_iterations if num_iterations is None else num_iterations
     losses, psnrs = [], []
     train_nerf.losses, train_nerf.psnrs = losses, psnrs
@@ -689,7 +723,7 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
         if i % config.scheduler_step_size == 0:                          # StepLR, train.py:95-96
             trainer.lr *= config.scheduler_gamma
         # the fine MSE; with a background or an opacity term the (fine) colour term
-        loss_v = float(trainer.loss_parts[0]) if (trainer.hierarchical or bg_kwargs) else float(loss)
+        loss_v = float(trainer.loss_parts[0]) if (trainer.hierarchical or bg_kwargs or dist_kwargs) else float(loss)
         psnr_v = -10.0 * math.log10(loss_v) if loss_v > 0 else float("inf")
         losses.append(loss_v)
         psnrs.append(psnr_v)

@@ -179,7 +179,76 @@ int nerf_train_hier_backward_bg(const float* packed, const float* packedT, const
                                 int64_t bg_rows, double acc_weight, float* rgb_final,
                                 float* coarse_final, nerf_stream_t stream);
 
+/* ---------------------------------------------------------------- distortion */
+/* The distortion loss of the ray weights (mip-NeRF 360), a penalty on the weights alone that is minimal
+ * when a ray's weight sits in one short interval.  Per ray of T samples (T = N for
+ * the dense and grid steps, N + Nf for a merged set; z non-decreasing), with w_i the forward's float
+ * weights alpha_i * (float)T_i and sample i's interval the compositor's, all in double from the float z:
+ *   delta_i = (double)z_{i+1} - (double)z_i  (i < T-1),  delta_{T-1} = (double)1e-3f
+ *   m_i     = (double)z_i + delta_i / 2                    inv = 1 / (far - near)
+ *   l_r         = inv * [ sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i ]
+ *   dl_r / dw_k = inv * [ 2 sum_j w_j |m_k - m_j| + (2/3) w_k delta_k ]
+ *   distortion loss = mean over the B rays of l_r
+ *   total = (colour + acc_weight * opacity) + dist_weight * distortion
+ * z carries no gradient.  T = 1: l = 0 and no gradient (the reference's per-sample tensors are empty).  A
+ * ray whose weights are all 0 has l = 0 and a gradient of exactly 0.  On a ray whose z descends somewhere
+ * the result is finite and otherwise unspecified.
+ *
+ * nerf_distortion is the stage, on any weights_out / z_out a render or a training forward returned:
+ * loss_rays (B) = (float)l_r and g_w (B,T) = (float)(scale * dl_r/dw_k), each nullable, every output
+ * rounded once from double; deterministic.  T in 1..4096 (else NERF_ERR_UNSUPPORTED); far <= near or a
+ * non-finite bound or scale is NERF_ERR_BAD_ARG.
+ *
+ * The _dist entries are the _bg entries with the distortion term: their arguments, then dist_weight,
+ * near and far in front of the stream.  loss grows by one float per part: dense and grid loss[2] the
+ * distortion loss; hierarchical six floats, fine colour, coarse colour, fine opacity, coarse opacity,
+ * fine distortion (over the N + Nf merged samples, gradient scale dist_weight / B), coarse distortion
+ * (over the N coarse samples, gradient scale coarse_weight * dist_weight / B).  Under a grid the dense
+ * zero-filled rows are used: a dead sample has weight 0.  With dist_weight == 0 an entry makes its _bg
+ * original's calls and returns its bits, and the distortion floats read 0; with every _bg option off as
+ * well the gradient is the plain MSE's plus the distortion term's.  The scratch (the weights, their
+ * gradient and the per-ray loss) lies in the workspace's gradient rows: the workspace sizes above hold.
+ * dist_weight negative or NaN, and with dist_weight > 0 far <= near or a non-finite bound, are
+ * NERF_ERR_BAD_ARG; every other refusal is the original's. */
+int nerf_distortion(const float* weights, const float* z_vals, int64_t B, int T, double near, double far,
+                    double scale, float* loss_rays, float* g_w, nerf_stream_t stream);
+int nerf_train_backward_dist(const float* packed, const float* packedT, const float* rgb_map,
+                             const float* target, int64_t B, int N, const float* app, int64_t app_rows,
+                             float* const* param_grads, float* dapp, float* loss /* 3 floats */,
+                             void* workspace, size_t ws_bytes, const float* alpha, const float* bg,
+                             int64_t bg_rows, double acc_weight, float* rgb_final, double dist_weight,
+                             double near, double far, nerf_stream_t stream);
+int nerf_train_occ_backward_dist(const float* packed, const float* packedT, const float* rgb_map,
+                                 const float* target, int64_t B, int N, int64_t M_live, const float* app,
+                                 int64_t app_rows, float* const* param_grads, float* dapp,
+                                 float* loss /* 3 floats */, void* workspace, size_t ws_bytes,
+                                 const float* alpha, const float* bg, int64_t bg_rows, double acc_weight,
+                                 float* rgb_final, double dist_weight, double near, double far,
+                                 nerf_stream_t stream);
+int nerf_train_hier_backward_dist(const float* packed, const float* packedT, const float* rgb_map,
+                                  const float* coarse_rgb, const float* target, int64_t B, int N, int Nf,
+                                  double coarse_weight, const float* app, int64_t app_rows,
+                                  float* const* param_grads, float* dapp, float* loss /* 6 floats */,
+                                  void* workspace, size_t ws_bytes, const float* alpha, const float* bg,
+                                  int64_t bg_rows, double acc_weight, float* rgb_final,
+                                  float* coarse_final, double dist_weight, double near, double far,
+                                  nerf_stream_t stream);
+
 /* -------------------------------------------------------------------- stages */
+/* nerf_composite_backward_grad_acc and nerf_composite_merged_backward_acc with g_w, a per-sample upstream
+ * gradient of the weights themselves ((B,N); merged: (B,N+Nf) in merged order; nullable = 0), added to the
+ * sample's d w right after g_acc.  With g_w null the _acc entry's launch and bits. */
+int nerf_composite_backward_grad_w(const float* rgb, const float* sigma, const float* z_vals,
+                                   const float* grad_rgb_map, const float* grad_depth_map, int64_t B,
+                                   int N, float* dsigma, float* drgb, const float* g_acc, float bd,
+                                   const float* g_w, nerf_stream_t stream);
+int nerf_composite_merged_backward_w(const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                                     const float* sigma_f, const uint16_t* merged_src,
+                                     const float* z_all, const float* grad_rgb_map,
+                                     const float* grad_depth_map, int64_t B, int N, int Nf,
+                                     int accumulate_coarse, float* dsigma_c, float* drgb_c,
+                                     float* dsigma_f, float* drgb_f, const float* g_acc, float bd,
+                                     const float* g_w, nerf_stream_t stream);
 /* nerf_composite_backward_grad and nerf_composite_merged_backward with g_acc (B, nullable = 0), the
  * upstream gradient of the ray's opacity acc = sum w (added to every d w of the ray), and bd, the
  * background depth the forward ran with: NaN = the normalised depth, else depth = sum w z + k bd and

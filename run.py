@@ -91,6 +91,9 @@ def parse_args(argv=None):
                    help="depth of the background: an empty ray's depth is this instead of 0 (render modes only)")
     p.add_argument('--acc_weight', type=float, default=0.0, metavar='W',
                    help='weight of the opacity loss mse(acc, alpha) (train mode)')
+    p.add_argument('--distortion_weight', type=float, default=0.0, metavar='W',
+                   help='weight of the distortion loss on the ray weights: fewer floaters and less haze in the '
+                        'depth map (train mode)')
     p.add_argument('--save_acc', action='store_true', help='write the opacity map acc_*.png beside the depth (render modes only)')
     args = p.parse_args(argv)
     if args.mode == 'train' and args.hierarchical and args.occupancy:
@@ -121,6 +124,10 @@ def parse_args(argv=None):
         p.error("--background_depth and --save_acc belong to the render modes (training writes no depth or opacity map)")
     if args.mode != 'train' and args.acc_weight:
         p.error("--acc_weight is for --mode train")
+    if not (args.distortion_weight >= 0.0 and np.isfinite(args.distortion_weight)):
+        p.error("--distortion_weight must be finite and >= 0")
+    if args.mode != 'train' and args.distortion_weight:
+        p.error("--distortion_weight is for --mode train")
     return args
 
 
@@ -322,8 +329,13 @@ def main(argv=None):
             bg_kw = dict(background=args.background, acc_weight=args.acc_weight)
             if rank == 0:
                 print(f"Training over background {args.background}, opacity loss weight {args.acc_weight:g}")
+        dist_kw = {}
+        if args.distortion_weight:   # the distortion loss on the ray weights (train.py, Trainer(distortion_weight=))
+            dist_kw = dict(distortion_weight=args.distortion_weight)
+            if rank == 0:
+                print(f"Training with the distortion loss, weight {args.distortion_weight:g}")
         model = train_nerf(config, dataset, save_dir=args.save_dir, num_iterations=args.iterations,   # run.py:347
-                           group=group, **occ_kw, **hier_kw, **bg_kw)
+                           group=group, **occ_kw, **hier_kw, **bg_kw, **dist_kw)
         if group is not None:
             dist.destroy_process_group()
         return 0
