@@ -38,6 +38,20 @@ def tile(x):
     return out.reshape(-1, 32, R // 8, 8).permute(0, 2, 1, 3).reshape(-1, R).contiguous()
 _V, _I64 = ctypes.c_void_p, ctypes.c_int64
 
+# The step backwards and the composite stage's _grad entries (include/nerfmi_train.h) are each "the
+# original's arguments, then the additions, then the stream".  The originals' own lists, without the stream:
+_GRADS = [ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t]    # param_grads_out .. ws_bytes
+_STEP = [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _I64] + _GRADS            # packed .. N, app, app_rows
+_OCC_STEP = _STEP[:6] + [_I64] + _STEP[6:]                                 # ... with M_live behind N
+_HIER_STEP = [_V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int, ctypes.c_double, _V, _I64] + _GRADS
+_STAGE = [_V, _V, _V, _V, _V, _I64, ctypes.c_int, _V, _V]                  # rgb .. drgb
+_MERGED_STAGE = [_V] * 8 + [_I64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _V, _V, _V, _V]
+# ... and the additions: the _bg tail (the hierarchical step: then coarse_final), the _dist tail behind it;
+# the _acc stages' (the _w stages: then g_w)
+_BG = [_V, _V, _I64, ctypes.c_double, _V]                                  # alpha, bg, bg_rows, acc_weight, rgb_final
+_DIST = [ctypes.c_double] * 3                                              # dist_weight, near, far
+_ACC = [_V, ctypes.c_float]                                                # g_acc, bd
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "nerf_last_error": (ctypes.c_char_p, []),
@@ -124,7 +138,7 @@ _SIGNATURES = {
     "nerf_mlp_forward_train": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V, _V, _V, _V, _V]),
     "nerf_composite_backward": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_float, _V, _V, _V,
                                                _V]),
-    "nerf_composite_backward_grad": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V]),
+    "nerf_composite_backward_grad": (ctypes.c_int, _STAGE + [_V]),
     "nerf_mlp_backward": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, _V, _V]),
     "nerf_param_grads_workspace_bytes": (ctypes.c_size_t, [_I64]),
     "nerf_param_grads": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, _V, _I64, _V, ctypes.POINTER(ctypes.c_void_p),
@@ -138,8 +152,7 @@ _SIGNATURES = {
     "nerf_train_forward": (ctypes.c_int, [_V, _V, _V, _I64, ctypes.c_double, ctypes.c_double, ctypes.c_int, _V,
                                           ctypes.c_int, _V, ctypes.c_uint64, _V, _I64, _V, _V, _V, _V, _V,
                                           ctypes.c_size_t, _V]),
-    "nerf_train_backward": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _I64,
-                                           ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V]),
+    "nerf_train_backward": (ctypes.c_int, _STEP + [_V]),
     # training with an occupancy grid (include/nerfmi_train.h)
     "nerf_train_occ_workspace_bytes": (ctypes.c_size_t, [_I64, ctypes.c_int]),
     "nerf_train_occ_sample": (ctypes.c_int, [_V, _V, _I64, ctypes.c_double, ctypes.c_double, ctypes.c_int, _V,
@@ -148,8 +161,7 @@ _SIGNATURES = {
                                              ctypes.c_size_t, _V]),
     "nerf_train_occ_forward": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, _I64, _V, _I64, _V, _V, _V, _V, _V,
                                               ctypes.c_size_t, _V]),
-    "nerf_train_occ_backward": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _I64, _V, _I64,
-                                               ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V]),
+    "nerf_train_occ_backward": (ctypes.c_int, _OCC_STEP + [_V]),
     "nerf_mlp_forward_train_live": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V, _I64, _V, _V, _V,
                                                    _V, _V, _V, _V]),
     # training with the hierarchical fine pass (include/nerfmi_train.h)
@@ -157,50 +169,26 @@ _SIGNATURES = {
     "nerf_train_hier_forward": (ctypes.c_int, [_V, _V, _V, _I64, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                                ctypes.c_int, _V, _V, ctypes.c_int, _V, _V, ctypes.c_uint64, _V, _I64,
                                                _V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_size_t, _V]),
-    "nerf_train_hier_backward": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
-                                                _V, _I64, ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t,
-                                                _V]),
+    "nerf_train_hier_backward": (ctypes.c_int, _HIER_STEP + [_V]),
     "nerf_sample_importance_src": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, ctypes.c_int, _V, _V, ctypes.c_uint64,
                                                   _V, _V, _V, _V]),
-    "nerf_composite_merged_backward": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int,
-                                                      ctypes.c_int, _V, _V, _V, _V, _V]),
+    "nerf_composite_merged_backward": (ctypes.c_int, _MERGED_STAGE + [_V]),
     # training with a background (include/nerfmi_train.h): the originals' arguments, then alpha, bg, bg_rows,
     # acc_weight, rgb_final (and coarse_final) / g_acc, bd in front of the stream
-    "nerf_train_backward_bg": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _I64,
-                                              ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V, _V,
-                                              _I64, ctypes.c_double, _V, _V]),
-    "nerf_train_occ_backward_bg": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _I64, _V, _I64,
-                                                  ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V,
-                                                  _V, _I64, ctypes.c_double, _V, _V]),
-    "nerf_train_hier_backward_bg": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int,
-                                                   ctypes.c_double, _V, _I64, ctypes.POINTER(ctypes.c_void_p), _V, _V,
-                                                   _V, ctypes.c_size_t, _V, _V, _I64, ctypes.c_double, _V, _V, _V]),
-    "nerf_composite_backward_grad_acc": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V,
-                                                        ctypes.c_float, _V]),
-    "nerf_composite_merged_backward_acc": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int,
-                                                          ctypes.c_int, ctypes.c_int, _V, _V, _V, _V, _V,
-                                                          ctypes.c_float, _V]),
+    "nerf_train_backward_bg": (ctypes.c_int, _STEP + _BG + [_V]),
+    "nerf_train_occ_backward_bg": (ctypes.c_int, _OCC_STEP + _BG + [_V]),
+    "nerf_train_hier_backward_bg": (ctypes.c_int, _HIER_STEP + _BG + [_V, _V]),
+    "nerf_composite_backward_grad_acc": (ctypes.c_int, _STAGE + _ACC + [_V]),
+    "nerf_composite_merged_backward_acc": (ctypes.c_int, _MERGED_STAGE + _ACC + [_V]),
     # training with the distortion loss (include/nerfmi_train.h): the _bg entries' arguments, then dist_weight,
     # near, far / the _acc stages' arguments, then g_w in front of the stream
     "nerf_distortion": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                        _V, _V, _V]),
-    "nerf_train_backward_dist": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _V, _I64,
-                                                ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V, _V,
-                                                _I64, ctypes.c_double, _V, ctypes.c_double, ctypes.c_double,
-                                                ctypes.c_double, _V]),
-    "nerf_train_occ_backward_dist": (ctypes.c_int, [_V, _V, _V, _V, _I64, ctypes.c_int, _I64, _V, _I64,
-                                                    ctypes.POINTER(ctypes.c_void_p), _V, _V, _V, ctypes.c_size_t, _V,
-                                                    _V, _I64, ctypes.c_double, _V, ctypes.c_double, ctypes.c_double,
-                                                    ctypes.c_double, _V]),
-    "nerf_train_hier_backward_dist": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, ctypes.c_int,
-                                                     ctypes.c_double, _V, _I64, ctypes.POINTER(ctypes.c_void_p), _V,
-                                                     _V, _V, ctypes.c_size_t, _V, _V, _I64, ctypes.c_double, _V, _V,
-                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _V]),
-    "nerf_composite_backward_grad_w": (ctypes.c_int, [_V, _V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, _V,
-                                                      ctypes.c_float, _V, _V]),
-    "nerf_composite_merged_backward_w": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int,
-                                                        ctypes.c_int, ctypes.c_int, _V, _V, _V, _V, _V,
-                                                        ctypes.c_float, _V, _V]),
+    "nerf_train_backward_dist": (ctypes.c_int, _STEP + _BG + _DIST + [_V]),
+    "nerf_train_occ_backward_dist": (ctypes.c_int, _OCC_STEP + _BG + _DIST + [_V]),
+    "nerf_train_hier_backward_dist": (ctypes.c_int, _HIER_STEP + _BG + [_V] + _DIST + [_V]),
+    "nerf_composite_backward_grad_w": (ctypes.c_int, _STAGE + _ACC + [_V, _V]),
+    "nerf_composite_merged_backward_w": (ctypes.c_int, _MERGED_STAGE + _ACC + [_V, _V]),
     # depth-aware post effects (include/nerfmi.h)
     "nerf_effect_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "nerf_depth_normalize": (ctypes.c_int, [_V, _I64, _V, _V, ctypes.c_size_t, _V]),

@@ -80,9 +80,9 @@ static size_t train_carve(int64_t B, int N, bool occ, void* base, TrainWs& w) {
   return c.at;
 }
 
-// An entry point's carve of the caller's workspace, refused when that is too small.
-static int train_ws(const char* fn, int64_t B, int N, bool occ, void* workspace, size_t ws_bytes, TrainWs& w) {
-  const size_t need = train_carve(B, N, occ, workspace, w);
+// An entry point's carve (`need`: what train_carve / hier_carve returned) of the caller's workspace,
+// refused when that is too small.
+static int check_ws(const char* fn, int64_t B, size_t ws_bytes, size_t need) {
   if (B > 0 && ws_bytes < need)
     return set_error(NERF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
   return NERF_OK;
@@ -106,10 +106,11 @@ static size_t param_floats(int p) {
     default: return 3;
   }
 }
-// ... and of a second gradient set with every tensor at a 64-float boundary
-static size_t grad_set_floats() {
+// ... and where tensor p starts in a second gradient set with every tensor at a 64-float boundary
+// (p = P_COUNT: the floats of the whole set)
+static size_t grad_set_offset(int p) {
   size_t n = 0;
-  for (int p = 0; p < P_COUNT; ++p) n += (param_floats(p) + 63) & ~(size_t)63;
+  for (int q = 0; q < p; ++q) n += (param_floats(q) + 63) & ~(size_t)63;
   return n;
 }
 
@@ -144,19 +145,12 @@ static size_t hier_carve(int64_t B, int N, int Nf, void* base, HierWs& h) {
   h.w_c = c.take<float>(b * N * 4);
   h.z_all = c.take<float>(b * T * 4);
   h.src = c.take<uint16_t>((b * T + 1) / 2 * 4);
-  h.grad2 = c.take<float>(grad_set_floats() * 4);
+  h.grad2 = c.take<float>(grad_set_offset(P_COUNT) * 4);
   h.dapp2 = c.take<float>(b * kAppDim * 4);
   const size_t wc = max_wgrad_floats((int64_t)b * N), wf = max_wgrad_floats((int64_t)b * Nf), wg = c.at;
   h.wgrad = c.take<float>((wc > wf ? wc : wf) * 4);
   h.wgrad_floats = (c.at - wg) / 4;
   return c.at;
-}
-
-static int hier_ws(const char* fn, int64_t B, int N, int Nf, void* workspace, size_t ws_bytes, HierWs& h) {
-  const size_t need = hier_carve(B, N, Nf, workspace, h);
-  if (B > 0 && ws_bytes < need)
-    return set_error(NERF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
-  return NERF_OK;
 }
 
 // What the last forward on a workspace was (a small host-side table keyed by workspace address): the
@@ -184,7 +178,7 @@ static bool last_forward(const void* ws, ForwardRecord& r) {
   r = it->second;
   return true;
 }
-// ---- the backward's head with a background (include/nerfmi_train.h "background")
+// ---- the background and opacity term (include/nerfmi_train.h "background")
 // The _bg entries' additions.  Off (no alpha, no background, acc_weight 0): the original entry's calls.
 struct BgLoss {
   const float* alpha;
@@ -215,7 +209,7 @@ static BgScratch bg_scratch(float* grad_rows, int64_t B) {
 static_assert(kGradRow >= 6 * 64, "the head's per-ray scratch fits in a ray's gradient rows");
 
 // ---- the distortion term (include/nerfmi_train.h "distortion")
-// The _dist entries' addition to the head above.  Off (weight 0): the _bg entry's calls.
+// The _dist entries' addition.  Off (weight 0): the _bg entry's calls.
 struct DistLoss {
   double weight, near, far;
   bool off() const { return weight == 0.0; }
@@ -242,42 +236,96 @@ static bool dist_scratch(float* grad_rows, int64_t rows, int64_t B, int T, DistS
   return 7 * b + 2 * bt <= (size_t)tile_rows(rows) * kGradRow;
 }
 
-// The head of sample set `in` (its per-ray regions are w's) from its per-ray gradient (g_rgb, g_acc), and
-// the two means: the composite once more for the opacity of the rows the forward left (its maps go to the
-// set's unused `maps` region), the per-ray loss, the composite backward in its _acc form into `out`.
-// With a distortion term (d non-null and on; `rows` = the samples of w's gradient rows) the composite
-// also leaves its weights in the scratch, distortion_kernel turns them into the per-ray loss and
-// g_w = weight d.weight / B * dl/dw, and the backward runs in its _w form with (g_rgb, g_acc, g_w).
-static int backward_head_bg(const TrainWs& w, const CompositeSamples& in, const CompositeGrads& out,
-                            const float* rgb_map, const float* target, const BgLoss& o, double weight, float* loss_rgb,
-                            float* loss_acc, float* rgb_final, hipStream_t s, const DistLoss* d = nullptr,
-                            int64_t rows = 0, float* loss_dist = nullptr) {
+// ---- what a backward entry was asked for, and the one head of all of them
+// The form is the entry (plain, _bg, _dist): it fixes which loss floats and outputs the caller gave.  The
+// options may all be off in any form; a plain entry's are.
+enum LossForm { kLossPlain, kLossBg, kLossDist };
+struct StepLoss {
+  LossForm form;
+  BgLoss bg;
+  DistLoss dist;
+  bool off() const { return bg.off() && dist.off(); }
+};
+
+static int check_step_loss(const char* fn, const StepLoss& spec, int64_t B) {
+  if (spec.form != kLossPlain)
+    if (int rc = check_bg_loss(fn, spec.bg, B)) return rc;
+  return spec.form == kLossDist ? check_dist_loss(fn, spec.dist) : NERF_OK;
+}
+
+// The loss layout of every entry: term k (0 colour, 1 opacity, 2 distortion) of part p (0 fine or the only
+// one, 1 coarse) of P parts is loss[k * P + p].  One part's slots: its loss floats (null for a term the form
+// lacks), its rgb_final (nullable), the weight of its loss and the samples whose gradient rows it owns.
+struct PartLoss {
+  float *rgb, *acc, *dist, *rgb_final;
+  double weight;
+  int64_t rows;
+};
+static PartLoss part_loss(const StepLoss& spec, float* loss, int p, int P, float* rgb_final, double weight,
+                          int64_t rows) {
+  return PartLoss{loss + p, spec.form != kLossPlain ? loss + P + p : nullptr,
+                  spec.form == kLossDist ? loss + 2 * P + p : nullptr, rgb_final, weight, rows};
+}
+
+static int zero_loss(const char* fn, float* slot, hipStream_t s) {   // (a null slot: the form lacks the term)
+  if (slot && hipMemsetAsync(slot, 0, 4, s) != hipSuccess)
+    return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
+  return NERF_OK;
+}
+
+// The backward's head of one part: sample set `in` (its per-ray regions and gradient rows are w's), its
+// gradients into `out`, its loss terms and rgb_final into `l`.  A term the form has and the options leave
+// off reads 0.  Two paths, by the options:
+//   all off: the composite backward of the MSE (train.py:87) and its mean, the original entries' calls and
+//     bits; rgb_final is rgb_map.
+//   any on: the composite once more for the opacity of the rows the forward left (its maps go to the set's
+//     unused `maps` region), the per-ray loss and gradient (g_rgb, g_acc), the composite backward in its _acc
+//     form, and the means.  With the distortion term on, the composite also leaves its weights in the
+//     scratch, distortion_kernel turns them into the per-ray loss and g_w = weight dist.weight / B * dl/dw,
+//     and the backward runs in its _w form with (g_rgb, g_acc, g_w).
+static int loss_head(const char* fn, const TrainWs& w, const CompositeSamples& in, const CompositeGrads& out,
+                     const float* rgb_map, const float* target, const StepLoss& spec, const PartLoss& l,
+                     hipStream_t s) {
   const int64_t B = in.B;
+  const BgLoss& o = spec.bg;
+  const DistLoss& d = spec.dist;
+  const bool dist = !d.off();
+  int rc;
+  if (!dist && (rc = zero_loss(fn, l.dist, s))) return rc;
+  if (spec.off()) {
+    const float scale = (float)(l.weight * (2.0 / (3.0 * (double)B)));
+    if ((rc = launch_composite_backward(in, upstream_loss(rgb_map, target, scale, w.sq_err), nullptr, out, s)))
+      return rc;
+    if ((rc = launch_loss(w.sq_err, B, l.rgb, s))) return rc;
+    if ((rc = zero_loss(fn, l.acc, s))) return rc;
+    if (l.rgb_final && hipMemcpyAsync(l.rgb_final, rgb_map, (size_t)B * 12, hipMemcpyDeviceToDevice, s) != hipSuccess)
+      return set_error(NERF_ERR_HIP, "%s: rgb_final copy failed", fn);
+    return NERF_OK;
+  }
   const BgScratch t = bg_scratch(w.grad, B);
   const CompositeBg acc_only{nullptr, 0, __builtin_nanf(""), t.acc};
   CompositeAccGrad acc{t.g_acc, __builtin_nanf("")};
-  const bool dist = d && !d->off();
   DistScratch ds{};
   const int T = in.merged ? in.N + in.Nf : in.N;
-  if (dist && !dist_scratch(w.grad, rows, B, T, ds))
+  if (dist && !dist_scratch(w.grad, l.rows, B, T, ds))
     return set_error(NERF_ERR_WORKSPACE, "distortion: the scratch of B=%lld T=%d exceeds the gradient rows",
                      (long long)B, T);
-  int rc;
   if ((rc = launch_composite(in, w.maps, w.maps + 3 * B, ds.weights, &acc_only, s))) return rc;
   if (dist) {
-    if ((rc = launch_distortion(ds.weights, in.z, B, T, 1.0 / (d->far - d->near), weight * d->weight / (double)B,
+    if ((rc = launch_distortion(ds.weights, in.z, B, T, 1.0 / (d.far - d.near), l.weight * d.weight / (double)B,
                                 ds.loss_rays, ds.g_w, s)))
       return rc;
     acc.g_w = ds.g_w;
   }
   if ((rc = launch_bg_loss(rgb_map, t.acc, target, o.alpha, o.bg_rows ? o.bg : nullptr, o.bg_rows > 1 ? 3 : 0,
-                           (float)o.acc_weight, (float)(weight * 2.0 / (3.0 * (double)B)),
-                           (float)(weight * 2.0 / (double)B), B, t.g_rgb, t.g_acc, w.sq_err, t.sq_acc, rgb_final, s)))
+                           (float)o.acc_weight, (float)(l.weight * 2.0 / (3.0 * (double)B)),
+                           (float)(l.weight * 2.0 / (double)B), B, t.g_rgb, t.g_acc, w.sq_err, t.sq_acc, l.rgb_final,
+                           s)))
     return rc;
   if ((rc = launch_composite_backward(in, upstream_grad(t.g_rgb, nullptr), &acc, out, s))) return rc;
-  if ((rc = launch_loss(w.sq_err, B, loss_rgb, s))) return rc;
-  if ((rc = launch_loss_rays(t.sq_acc, B, loss_acc, s))) return rc;
-  return dist ? launch_loss_rays(ds.loss_rays, B, loss_dist, s) : NERF_OK;
+  if ((rc = launch_loss(w.sq_err, B, l.rgb, s))) return rc;
+  if ((rc = launch_loss_rays(t.sq_acc, B, l.acc, s))) return rc;
+  return dist ? launch_loss_rays(ds.loss_rays, B, l.dist, s) : NERF_OK;
 }
 }  // namespace nerf
 
@@ -321,13 +369,48 @@ int nerf_mlp_forward_train(const float* packed, const float* origins, const floa
                     enc_d, masks);
 }
 
+// The checks of the composite stage's entries, one per sample-set kind (`ptrs`: every pointer the entry
+// requires is there)
+static int check_dense_stage(const char* fn, int64_t B, int N, bool ptrs) {
+  REQUIRE(B >= 0, "%s: B=%lld", fn, (long long)B);
+  if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "%s: N=%d (1..4096)", fn, N);
+  REQUIRE(B == 0 || ptrs, "%s: null pointer", fn);
+  return NERF_OK;
+}
+static int check_merged_stage(const char* fn, int64_t B, int N, int Nf, bool ptrs) {
+  REQUIRE(B >= 0, "%s: B=%lld", fn, (long long)B);
+  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
+    return set_error(NERF_ERR_UNSUPPORTED, "%s: N=%d (1..256) Nf=%d (1..1024)", fn, N, Nf);
+  REQUIRE(B == 0 || ptrs, "%s: null pointer", fn);
+  return NERF_OK;
+}
+// ... and the _grad entries of either kind: plain (acc null), _acc and _w
+static int dense_stage_grad(const char* fn, const float* rgb, const float* sigma, const float* z_vals,
+                            const float* grad_rgb_map, const float* grad_depth_map, int64_t B, int N, float* dsigma,
+                            float* drgb, const CompositeAccGrad* acc, nerf_stream_t stream) {
+  if (int rc = check_dense_stage(fn, B, N, rgb && sigma && z_vals && dsigma && drgb)) return rc;
+  return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_grad(grad_rgb_map, grad_depth_map),
+                                   acc, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
+}
+static int merged_stage_grad(const char* fn, const float* rgb_c, const float* sigma_c, const float* rgb_f,
+                             const float* sigma_f, const uint16_t* src, const float* z_all, const float* grad_rgb_map,
+                             const float* grad_depth_map, int64_t B, int N, int Nf, int accumulate_coarse,
+                             float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f, const CompositeAccGrad* acc,
+                             nerf_stream_t stream) {
+  if (int rc = check_merged_stage(fn, B, N, Nf, rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c &&
+                                                    drgb_c && dsigma_f && drgb_f))
+    return rc;
+  return launch_composite_backward(merged_samples(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, B, N, Nf),
+                                   upstream_grad(grad_rgb_map, grad_depth_map), acc,
+                                   {dsigma_c, drgb_c, dsigma_f, drgb_f, accumulate_coarse}, (hipStream_t)stream);
+}
+
 int nerf_composite_backward(const float* rgb, const float* sigma, const float* z_vals, const float* rgb_map,
                             const float* target, int64_t B, int N, float scale, float* dsigma, float* drgb,
                             float* sq_err, nerf_stream_t stream) {
-  REQUIRE(B >= 0, "nerf_composite_backward: B=%lld", (long long)B);
-  if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward: N=%d (1..4096)", N);
-  REQUIRE(B == 0 || (rgb && sigma && z_vals && rgb_map && target && dsigma && drgb && sq_err),
-          "nerf_composite_backward: null pointer");
+  if (int rc = check_dense_stage("nerf_composite_backward", B, N,
+                                 rgb && sigma && z_vals && rgb_map && target && dsigma && drgb && sq_err))
+    return rc;
   return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_loss(rgb_map, target, scale, sq_err),
                                    nullptr, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
 }
@@ -335,11 +418,8 @@ int nerf_composite_backward(const float* rgb, const float* sigma, const float* z
 int nerf_composite_backward_grad(const float* rgb, const float* sigma, const float* z_vals, const float* grad_rgb_map,
                                  const float* grad_depth_map, int64_t B, int N, float* dsigma, float* drgb,
                                  nerf_stream_t stream) {
-  REQUIRE(B >= 0, "nerf_composite_backward_grad: B=%lld", (long long)B);
-  if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward_grad: N=%d (1..4096)", N);
-  REQUIRE(B == 0 || (rgb && sigma && z_vals && dsigma && drgb), "nerf_composite_backward_grad: null pointer");
-  return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_grad(grad_rgb_map, grad_depth_map),
-                                   nullptr, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
+  return dense_stage_grad("nerf_composite_backward_grad", rgb, sigma, z_vals, grad_rgb_map, grad_depth_map, B, N,
+                          dsigma, drgb, nullptr, stream);
 }
 
 int nerf_mlp_backward(const float* packed, const float* packedT, const float* save, const uint32_t* masks,
@@ -637,41 +717,19 @@ static int forward_tail(const char* fn, const TrainWs& w, int64_t B, int N, floa
   return NERF_OK;
 }
 
-// the backward's head: the composite backward of the MSE (train.py:87) into dsigma / drgb, and the loss
-static int backward_head(const TrainWs& w, const float* rgb_map, const float* target, int64_t B, int N, float* loss,
-                         hipStream_t s) {
-  const float scale = (float)(2.0 / (3.0 * (double)B));
-  if (int rc = launch_composite_backward(w.samples(B, N), upstream_loss(rgb_map, target, scale, w.sq_err), nullptr,
-                                         w.grads(), s))
-    return rc;
-  return launch_loss(w.sq_err, B, loss, s);
-}
-
-// with every option off: the opacity parts of the loss read 0 and rgb_final is rgb_map
-static int bg_off_outputs(const char* fn, float* loss_acc, int n_acc, float* rgb_final, const float* rgb_map, int64_t B,
-                          hipStream_t s) {
-  if (hipMemsetAsync(loss_acc, 0, (size_t)n_acc * 4, s) != hipSuccess)
-    return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
-  if (rgb_final && B > 0 &&
-      hipMemcpyAsync(rgb_final, rgb_map, (size_t)B * 12, hipMemcpyDeviceToDevice, s) != hipSuccess)
-    return set_error(NERF_ERR_HIP, "%s: rgb_final copy failed", fn);
-  return NERF_OK;
-}
-
-// The head of the dense step and, on its zero-filled dense rows (a dead sample has weight 0), of the
-// occupancy step; bgl null: the entry without a background.
-// dl null: no distortion entry; off: its float (loss[2]) reads 0 after the _bg entry's calls.
-static int dense_head(const char* fn, const TrainWs& w, const float* rgb_map, const float* target, int64_t B, int N,
-                      const BgLoss* bgl, float* loss, float* rgb_final, hipStream_t s, const DistLoss* dl = nullptr) {
-  if (dl && !dl->off())
-    return backward_head_bg(w, w.samples(B, N), w.grads(), rgb_map, target, *bgl, 1.0, loss, loss + 1, rgb_final, s, dl,
-                            B * N, loss + 2);
-  if (dl && hipMemsetAsync(loss + 2, 0, 4, s) != hipSuccess)
-    return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
-  if (bgl && !bgl->off())
-    return backward_head_bg(w, w.samples(B, N), w.grads(), rgb_map, target, *bgl, 1.0, loss, loss + 1, rgb_final, s);
-  if (int rc = backward_head(w, rgb_map, target, B, N, loss, s)) return rc;
-  return bgl ? bg_off_outputs(fn, loss + 1, 1, rgb_final, rgb_map, B, s) : NERF_OK;
+// The forward of the dense step and the coarse pass of the hierarchical one, into sample set w: ray features,
+// stratified positions, the MLP with saves.
+static int coarse_forward(const float* packed, const float* rays_o, const float* rays_d, int64_t B, double near,
+                          double far, int N, const float* t_vals, int perturb, const float* t_rand, uint64_t seed,
+                          const float* app, int64_t app_rows, const TrainWs& w, hipStream_t s) {
+  int rc;
+  // the directions normalised (render.py:19) by the ray-feature kernel, which writes them to w.dirs
+  if ((rc = launch_ray_features(packed, rays_d, B, app, app_rows, w.feat, s, w.encd, w.dirs))) return rc;
+  if ((rc = launch_stratified(rays_o, w.dirs, B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand, seed,
+                              w.z, nullptr, s)))
+    return rc;                                                                                          // :22
+  return launch_mlp(packed, rays_o, w.dirs, w.z, B, N, w.feat, w.rgb, w.sigma, nullptr, 0, s, w.save, w.encd,
+                    w.masks);                                                                           // :49
 }
 
 size_t nerf_train_workspace_bytes(int64_t B, int N) {
@@ -700,36 +758,29 @@ int nerf_train_forward(const float* packed, const float* rays_o, const float* ra
           "nerf_train_forward: null pointer");
   TrainWs w;
   int rc;
-  if ((rc = train_ws("nerf_train_forward", B, N, false, workspace, ws_bytes, w))) return rc;
+  if ((rc = check_ws("nerf_train_forward", B, ws_bytes, train_carve(B, N, false, workspace, w)))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  // the directions normalised (render.py:19) by the ray-feature kernel, which writes them to w.dirs
-  if ((rc = launch_ray_features(packed, rays_d, B, app, app_rows, w.feat, s, w.encd, w.dirs))) return rc;
-  if ((rc = launch_stratified(rays_o, w.dirs, B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand, seed,
-                              w.z, nullptr, s)))
-    return rc;                                                                                          // :22
-  if ((rc = launch_mlp(packed, rays_o, w.dirs, w.z, B, N, w.feat, w.rgb, w.sigma, nullptr, 0, s, w.save, w.encd,
-                       w.masks)))
-    return rc;                                                                                          // :49
+  if ((rc = coarse_forward(packed, rays_o, rays_d, B, near, far, N, t_vals, perturb, t_rand, seed, app, app_rows, w, s)))
+    return rc;
   remember_forward(workspace, {g_mlp_arith, kStepDense, 0});
   return forward_tail("nerf_train_forward", w, B, N, rgb_map, depth_map, weights_out, z_out, s);
 }
 
-// nerf_train_backward (bgl null) and nerf_train_backward_bg
+// nerf_train_backward and its _bg and _dist forms (rgb_final: null in the plain form)
 static int train_backward(const char* fn, const float* packed, const float* packedT, const float* rgb_map,
                           const float* target, int64_t B, int N, const float* app, int64_t app_rows,
                           float* const* param_grads_out, float* dapp, float* loss, void* workspace, size_t ws_bytes,
-                          const BgLoss* bgl, float* rgb_final, nerf_stream_t stream, const DistLoss* dl = nullptr) {
+                          const StepLoss& spec, float* rgb_final, nerf_stream_t stream) {
   REQUIRE(B >= 0 && N >= 1 && N <= 4096, "%s: B=%lld N=%d", fn, (long long)B, N);
   REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "%s: app_rows=%lld", fn, (long long)app_rows);
   int rc;
-  if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
-  if (dl && (rc = check_dist_loss(fn, *dl))) return rc;
+  if ((rc = check_step_loss(fn, spec, B))) return rc;
   if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
                                 workspace)))
     return rc;
   if (B == 0) return NERF_OK;
   TrainWs w;
-  if ((rc = train_ws(fn, B, N, false, workspace, ws_bytes, w))) return rc;
+  if ((rc = check_ws(fn, B, ws_bytes, train_carve(B, N, false, workspace, w)))) return rc;
   hipStream_t s = (hipStream_t)stream;
   // the mask rows exist only when this workspace's forward ran under f16x3; the backward's kernels
   // follow the arithmetic in force now (an f16x3 backward after an f32 forward reads the ReLU masks
@@ -739,7 +790,9 @@ static int train_backward(const char* fn, const float* packed, const float* pack
     return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_forward wrote this workspace", fn);
   const uint32_t* masks = fwd.arith == NERF_ARITH_F16X3 ? w.masks : nullptr;
   const int64_t M = B * N;
-  if ((rc = dense_head(fn, w, rgb_map, target, B, N, bgl, loss, rgb_final, s, dl))) return rc;
+  if ((rc = loss_head(fn, w, w.samples(B, N), w.grads(), rgb_map, target, spec,
+                      part_loss(spec, loss, 0, 1, rgb_final, 1.0, M), s)))
+    return rc;
   if ((rc = launch_mlp_backward(packed, packedT, w.save, masks, w.sigma, w.rgb, w.dsigma, w.drgb, M, w.grad, s,
                                 /*store_dhd=*/!fused_ray_sums(N))))
     return rc;
@@ -750,7 +803,7 @@ int nerf_train_backward(const float* packed, const float* packedT, const float* 
                         int64_t B, int N, const float* app, int64_t app_rows, float* const* param_grads_out,
                         float* dapp, float* loss, void* workspace, size_t ws_bytes, nerf_stream_t stream) {
   return train_backward("nerf_train_backward", packed, packedT, rgb_map, target, B, N, app, app_rows, param_grads_out,
-                        dapp, loss, workspace, ws_bytes, nullptr, nullptr, stream);
+                        dapp, loss, workspace, ws_bytes, StepLoss{kLossPlain, {}, {}}, nullptr, stream);
 }
 
 int nerf_train_backward_bg(const float* packed, const float* packedT, const float* rgb_map, const float* target,
@@ -758,9 +811,9 @@ int nerf_train_backward_bg(const float* packed, const float* packedT, const floa
                            float* dapp, float* loss, void* workspace, size_t ws_bytes, const float* alpha,
                            const float* bg, int64_t bg_rows, double acc_weight, float* rgb_final,
                            nerf_stream_t stream) {
-  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  const StepLoss spec{kLossBg, {alpha, bg, bg_rows, acc_weight}, {}};
   return train_backward("nerf_train_backward_bg", packed, packedT, rgb_map, target, B, N, app, app_rows,
-                        param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream);
+                        param_grads_out, dapp, loss, workspace, ws_bytes, spec, rgb_final, stream);
 }
 
 int nerf_train_backward_dist(const float* packed, const float* packedT, const float* rgb_map, const float* target,
@@ -768,10 +821,9 @@ int nerf_train_backward_dist(const float* packed, const float* packedT, const fl
                              float* dapp, float* loss, void* workspace, size_t ws_bytes, const float* alpha,
                              const float* bg, int64_t bg_rows, double acc_weight, float* rgb_final, double dist_weight,
                              double near, double far, nerf_stream_t stream) {
-  const BgLoss o{alpha, bg, bg_rows, acc_weight};
-  const DistLoss d{dist_weight, near, far};
+  const StepLoss spec{kLossDist, {alpha, bg, bg_rows, acc_weight}, {dist_weight, near, far}};
   return train_backward("nerf_train_backward_dist", packed, packedT, rgb_map, target, B, N, app, app_rows,
-                        param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream, &d);
+                        param_grads_out, dapp, loss, workspace, ws_bytes, spec, rgb_final, stream);
 }
 
 int nerf_train_occ_sample(const float* rays_o, const float* rays_d, int64_t B, double near, double far, int N,
@@ -784,7 +836,7 @@ int nerf_train_occ_sample(const float* rays_o, const float* rays_d, int64_t B, d
   REQUIRE(B == 0 || (rays_o && rays_d && t_vals && workspace), "nerf_train_occ_sample: null pointer");
   if (G < 1 || G > 1024) return set_error(NERF_ERR_UNSUPPORTED, "nerf_train_occ_sample: G=%d outside 1..1024", G);
   TrainWs w;
-  if ((rc = train_ws("nerf_train_occ_sample", B, N, true, workspace, ws_bytes, w))) return rc;
+  if ((rc = check_ws("nerf_train_occ_sample", B, ws_bytes, train_carve(B, N, true, workspace, w)))) return rc;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = launch_normalize(rays_d, B, w.dirs, s))) return rc;                                          // render.py:19
   if ((rc = launch_stratified(rays_o, w.dirs, B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand, seed,
@@ -803,7 +855,7 @@ int nerf_train_occ_forward(const float* packed, const float* rays_o, int64_t B, 
   REQUIRE(packed && rays_o && rgb_map && depth_map && workspace && (app_rows == 0 || app),
           "nerf_train_occ_forward: null pointer");
   TrainWs w;
-  if ((rc = train_ws("nerf_train_occ_forward", B, N, true, workspace, ws_bytes, w))) return rc;
+  if ((rc = check_ws("nerf_train_occ_forward", B, ws_bytes, train_carve(B, N, true, workspace, w)))) return rc;
   hipStream_t s = (hipStream_t)stream;
   // w.dirs holds the normalised directions (nerf_train_occ_sample): the features from them as they are
   if ((rc = launch_ray_features(packed, w.dirs, B, app, app_rows, w.feat, s, w.encd, nullptr))) return rc;
@@ -814,28 +866,30 @@ int nerf_train_occ_forward(const float* packed, const float* rays_o, int64_t B, 
   return forward_tail("nerf_train_occ_forward", w, B, N, rgb_map, depth_map, weights_out, z_out, s);
 }
 
-// nerf_train_occ_backward (bgl null) and nerf_train_occ_backward_bg
+// nerf_train_occ_backward and its _bg and _dist forms.  The head runs on the zero-filled dense rows: a dead
+// sample has weight 0.
 static int train_occ_backward(const char* fn, const float* packed, const float* packedT, const float* rgb_map,
                               const float* target, int64_t B, int N, int64_t M_live, const float* app,
                               int64_t app_rows, float* const* param_grads_out, float* dapp, float* loss,
-                              void* workspace, size_t ws_bytes, const BgLoss* bgl, float* rgb_final,
-                              nerf_stream_t stream, const DistLoss* dl = nullptr) {
+                              void* workspace, size_t ws_bytes, const StepLoss& spec, float* rgb_final,
+                              nerf_stream_t stream) {
   int rc;
   if ((rc = check_occ_step(fn, "step", B, N, M_live, app_rows))) return rc;
-  if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
-  if (dl && (rc = check_dist_loss(fn, *dl))) return rc;
+  if ((rc = check_step_loss(fn, spec, B))) return rc;
   if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
                                 workspace)))
     return rc;
   if (B == 0) return NERF_OK;
   TrainWs w;
-  if ((rc = train_ws(fn, B, N, true, workspace, ws_bytes, w))) return rc;
+  if ((rc = check_ws(fn, B, ws_bytes, train_carve(B, N, true, workspace, w)))) return rc;
   ForwardRecord fwd;
   if (!last_forward(workspace, fwd) || fwd.kind != kStepOcc || fwd.M_live != M_live)
     return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_occ_forward with M_live=%lld wrote this "
                      "workspace", fn, (long long)M_live);
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = dense_head(fn, w, rgb_map, target, B, N, bgl, loss, rgb_final, s, dl))) return rc;
+  if ((rc = loss_head(fn, w, w.samples(B, N), w.grads(), rgb_map, target, spec,
+                      part_loss(spec, loss, 0, 1, rgb_final, 1.0, B * N), s)))
+    return rc;
   if (M_live == 0) {   // every sample dead: sigma = 0 is a constant of the step, every gradient is zero
     for (int p = 0; p < P_COUNT; ++p)
       if (hipMemsetAsync(param_grads_out[p], 0, param_floats(p) * 4, s) != hipSuccess)
@@ -857,7 +911,8 @@ int nerf_train_occ_backward(const float* packed, const float* packedT, const flo
                             float* const* param_grads_out, float* dapp, float* loss, void* workspace, size_t ws_bytes,
                             nerf_stream_t stream) {
   return train_occ_backward("nerf_train_occ_backward", packed, packedT, rgb_map, target, B, N, M_live, app, app_rows,
-                            param_grads_out, dapp, loss, workspace, ws_bytes, nullptr, nullptr, stream);
+                            param_grads_out, dapp, loss, workspace, ws_bytes, StepLoss{kLossPlain, {}, {}}, nullptr,
+                            stream);
 }
 
 int nerf_train_occ_backward_bg(const float* packed, const float* packedT, const float* rgb_map, const float* target,
@@ -865,9 +920,9 @@ int nerf_train_occ_backward_bg(const float* packed, const float* packedT, const 
                                float* const* param_grads_out, float* dapp, float* loss, void* workspace,
                                size_t ws_bytes, const float* alpha, const float* bg, int64_t bg_rows,
                                double acc_weight, float* rgb_final, nerf_stream_t stream) {
-  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  const StepLoss spec{kLossBg, {alpha, bg, bg_rows, acc_weight}, {}};
   return train_occ_backward("nerf_train_occ_backward_bg", packed, packedT, rgb_map, target, B, N, M_live, app, app_rows,
-                            param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream);
+                            param_grads_out, dapp, loss, workspace, ws_bytes, spec, rgb_final, stream);
 }
 
 int nerf_train_occ_backward_dist(const float* packed, const float* packedT, const float* rgb_map, const float* target,
@@ -876,10 +931,9 @@ int nerf_train_occ_backward_dist(const float* packed, const float* packedT, cons
                                  size_t ws_bytes, const float* alpha, const float* bg, int64_t bg_rows,
                                  double acc_weight, float* rgb_final, double dist_weight, double near, double far,
                                  nerf_stream_t stream) {
-  const BgLoss o{alpha, bg, bg_rows, acc_weight};
-  const DistLoss d{dist_weight, near, far};
+  const StepLoss spec{kLossDist, {alpha, bg, bg_rows, acc_weight}, {dist_weight, near, far}};
   return train_occ_backward("nerf_train_occ_backward_dist", packed, packedT, rgb_map, target, B, N, M_live, app,
-                            app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, &o, rgb_final, stream, &d);
+                            app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, spec, rgb_final, stream);
 }
 
 // ------------------------------------------------------------- the hierarchical step
@@ -918,15 +972,10 @@ int nerf_train_hier_forward(const float* packed, const float* rays_o, const floa
               workspace && (app_rows == 0 || app),
           "%s: null pointer", fn);
   HierWs h;
-  if ((rc = hier_ws(fn, B, N, Nf, workspace, ws_bytes, h))) return rc;
+  if ((rc = check_ws(fn, B, ws_bytes, hier_carve(B, N, Nf, workspace, h)))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const TrainWs &c = h.c, &f = h.f;
-  // the coarse pass: nerf_train_forward's sequence
-  if ((rc = launch_ray_features(packed, rays_d, B, app, app_rows, c.feat, s, c.encd, c.dirs))) return rc;
-  if ((rc = launch_stratified(rays_o, c.dirs, B, (float)near, (float)(far - near), N, t_vals, perturb, t_rand, seed, c.z,
-                              nullptr, s)))
-    return rc;
-  if ((rc = launch_mlp(packed, rays_o, c.dirs, c.z, B, N, c.feat, c.rgb, c.sigma, nullptr, 0, s, c.save, c.encd, c.masks)))
+  if ((rc = coarse_forward(packed, rays_o, rays_d, B, near, far, N, t_vals, perturb, t_rand, seed, app, app_rows, c, s)))
     return rc;
   remember_forward(workspace, {g_mlp_arith, kStepHier, 0});
   float* wc = coarse_weights_out ? coarse_weights_out : h.w_c;
@@ -944,17 +993,16 @@ int nerf_train_hier_forward(const float* packed, const float* rays_o, const floa
   return NERF_OK;
 }
 
-// nerf_train_hier_backward (bgl null) and nerf_train_hier_backward_bg
+// nerf_train_hier_backward and its _bg and _dist forms (rgb_final, coarse_final: null in the plain form)
 static int train_hier_backward(const char* fn, const float* packed, const float* packedT, const float* rgb_map,
                                const float* coarse_rgb, const float* target, int64_t B, int N, int Nf,
                                double coarse_weight, const float* app, int64_t app_rows,
                                float* const* param_grads_out, float* dapp, float* loss, void* workspace,
-                               size_t ws_bytes, const BgLoss* bgl, float* rgb_final, float* coarse_final,
-                               nerf_stream_t stream, const DistLoss* dl = nullptr) {
+                               size_t ws_bytes, const StepLoss& spec, float* rgb_final, float* coarse_final,
+                               nerf_stream_t stream) {
   int rc;
   if ((rc = check_hier_shape(fn, B, N, Nf))) return rc;
-  if (bgl && (rc = check_bg_loss(fn, *bgl, B))) return rc;
-  if (dl && (rc = check_dist_loss(fn, *dl))) return rc;
+  if ((rc = check_step_loss(fn, spec, B))) return rc;
   REQUIRE(app_rows == 0 || app_rows == 1 || app_rows == B, "%s: app_rows=%lld", fn, (long long)app_rows);
   REQUIRE(coarse_weight >= 0.0 && coarse_weight <= 3.0e38, "%s: coarse_weight=%g", fn, coarse_weight);
   if ((rc = check_backward_ptrs(fn, packed, packedT, rgb_map, target, B, app, app_rows, param_grads_out, loss,
@@ -963,57 +1011,24 @@ static int train_hier_backward(const char* fn, const float* packed, const float*
   REQUIRE(B == 0 || coarse_rgb, "%s: null pointer", fn);
   if (B == 0) return NERF_OK;
   HierWs h;
-  if ((rc = hier_ws(fn, B, N, Nf, workspace, ws_bytes, h))) return rc;
+  if ((rc = check_ws(fn, B, ws_bytes, hier_carve(B, N, Nf, workspace, h)))) return rc;
   ForwardRecord fwd;
   if (!last_forward(workspace, fwd) || fwd.kind != kStepHier)
     return set_error(NERF_ERR_BAD_ARG, "%s: no nerf_train_hier_forward wrote this workspace", fn);
   hipStream_t s = (hipStream_t)stream;
   const TrainWs &c = h.c, &f = h.f;
   const bool f16 = fwd.arith == NERF_ARITH_F16X3;
-  const double mse_scale = 2.0 / (3.0 * (double)B);
-  // the coarse composite's term, then the merged composite's on top of it in the coarse rows
-  const bool dist = dl && !dl->off();   // off: the _bg entry's calls, and the two distortion floats read 0
-  if (dl && !dist && hipMemsetAsync(loss + 4, 0, 8, s) != hipSuccess)
-    return set_error(NERF_ERR_HIP, "%s: hipMemsetAsync failed", fn);
-  if (dist) {
-    // the _bg heads with the distortion term of each part: loss + 4 fine, loss + 5 coarse
-    if ((rc = backward_head_bg(c, c.samples(B, N), c.grads(), coarse_rgb, target, *bgl, coarse_weight, loss + 1,
-                               loss + 3, coarse_final, s, dl, B * N, loss + 5)))
-      return rc;
-    if ((rc = backward_head_bg(f, h.merged(B, N, Nf), h.merged_grads(), rgb_map, target, *bgl, 1.0, loss, loss + 2,
-                               rgb_final, s, dl, B * Nf, loss + 4)))
-      return rc;
-  } else if (bgl && !bgl->off()) {
-    // the same two terms from each part's per-ray head (the coarse part's scaled by coarse_weight); loss:
-    // fine colour, coarse colour, fine opacity, coarse opacity
-    if ((rc = backward_head_bg(c, c.samples(B, N), c.grads(), coarse_rgb, target, *bgl, coarse_weight, loss + 1,
-                               loss + 3, coarse_final, s)))
-      return rc;
-    if ((rc = backward_head_bg(f, h.merged(B, N, Nf), h.merged_grads(), rgb_map, target, *bgl, 1.0, loss, loss + 2,
-                               rgb_final, s)))
-      return rc;
-  } else {
-    if ((rc = launch_composite_backward(c.samples(B, N),
-                                        upstream_loss(coarse_rgb, target, (float)(coarse_weight * mse_scale), c.sq_err),
-                                        nullptr, c.grads(), s)))
-      return rc;
-    if ((rc = launch_composite_backward(h.merged(B, N, Nf), upstream_loss(rgb_map, target, (float)mse_scale, f.sq_err),
-                                        nullptr, h.merged_grads(), s)))
-      return rc;
-    if ((rc = launch_loss(f.sq_err, B, loss, s))) return rc;
-    if ((rc = launch_loss(c.sq_err, B, loss + 1, s))) return rc;
-    if (bgl) {
-      if ((rc = bg_off_outputs(fn, loss + 2, 2, rgb_final, rgb_map, B, s))) return rc;
-      if ((rc = bg_off_outputs(fn, loss + 2, 2, coarse_final, coarse_rgb, B, s))) return rc;
-    }
-  }
+  // The coarse part's head (scaled by coarse_weight), then the merged one's, which adds into the coarse rows;
+  // both before the first launch_mlp_backward, which reads those rows and overwrites the heads' scratch.
+  if ((rc = loss_head(fn, c, c.samples(B, N), c.grads(), coarse_rgb, target, spec,
+                      part_loss(spec, loss, 1, 2, coarse_final, coarse_weight, B * N), s)))
+    return rc;
+  if ((rc = loss_head(fn, f, h.merged(B, N, Nf), h.merged_grads(), rgb_map, target, spec,
+                      part_loss(spec, loss, 0, 2, rgb_final, 1.0, B * Nf), s)))
+    return rc;
   // the fine part's gradients go to the workspace's second set
   float* g2[P_COUNT];
-  size_t at = 0;
-  for (int p = 0; p < P_COUNT; ++p) {
-    g2[p] = h.grad2 + at;
-    at += (param_floats(p) + 63) & ~(size_t)63;
-  }
+  for (int p = 0; p < P_COUNT; ++p) g2[p] = h.grad2 + grad_set_offset(p);
   if ((rc = launch_mlp_backward(packed, packedT, c.save, f16 ? c.masks : nullptr, c.sigma, c.rgb, c.dsigma, c.drgb, B * N,
                                 c.grad, s, /*store_dhd=*/!fused_ray_sums(N))))
     return rc;
@@ -1045,8 +1060,8 @@ int nerf_train_hier_backward(const float* packed, const float* packedT, const fl
                              int64_t app_rows, float* const* param_grads_out, float* dapp, float* loss,
                              void* workspace, size_t ws_bytes, nerf_stream_t stream) {
   return train_hier_backward("nerf_train_hier_backward", packed, packedT, rgb_map, coarse_rgb, target, B, N, Nf,
-                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, nullptr,
-                             nullptr, nullptr, stream);
+                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes,
+                             StepLoss{kLossPlain, {}, {}}, nullptr, nullptr, stream);
 }
 
 int nerf_train_hier_backward_bg(const float* packed, const float* packedT, const float* rgb_map,
@@ -1055,9 +1070,9 @@ int nerf_train_hier_backward_bg(const float* packed, const float* packedT, const
                                 float* const* param_grads_out, float* dapp, float* loss, void* workspace,
                                 size_t ws_bytes, const float* alpha, const float* bg, int64_t bg_rows,
                                 double acc_weight, float* rgb_final, float* coarse_final, nerf_stream_t stream) {
-  const BgLoss o{alpha, bg, bg_rows, acc_weight};
+  const StepLoss spec{kLossBg, {alpha, bg, bg_rows, acc_weight}, {}};
   return train_hier_backward("nerf_train_hier_backward_bg", packed, packedT, rgb_map, coarse_rgb, target, B, N, Nf,
-                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, &o,
+                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, spec,
                              rgb_final, coarse_final, stream);
 }
 
@@ -1068,11 +1083,10 @@ int nerf_train_hier_backward_dist(const float* packed, const float* packedT, con
                                   size_t ws_bytes, const float* alpha, const float* bg, int64_t bg_rows,
                                   double acc_weight, float* rgb_final, float* coarse_final, double dist_weight,
                                   double near, double far, nerf_stream_t stream) {
-  const BgLoss o{alpha, bg, bg_rows, acc_weight};
-  const DistLoss d{dist_weight, near, far};
+  const StepLoss spec{kLossDist, {alpha, bg, bg_rows, acc_weight}, {dist_weight, near, far}};
   return train_hier_backward("nerf_train_hier_backward_dist", packed, packedT, rgb_map, coarse_rgb, target, B, N, Nf,
-                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, &o,
-                             rgb_final, coarse_final, stream, &d);
+                             coarse_weight, app, app_rows, param_grads_out, dapp, loss, workspace, ws_bytes, spec,
+                             rgb_final, coarse_final, stream);
 }
 
 int nerf_distortion(const float* weights, const float* z_vals, int64_t B, int T, double near, double far, double scale,
@@ -1088,12 +1102,9 @@ int nerf_distortion(const float* weights, const float* z_vals, int64_t B, int T,
 int nerf_composite_backward_grad_w(const float* rgb, const float* sigma, const float* z_vals, const float* grad_rgb_map,
                                    const float* grad_depth_map, int64_t B, int N, float* dsigma, float* drgb,
                                    const float* g_acc, float bd, const float* g_w, nerf_stream_t stream) {
-  REQUIRE(B >= 0, "nerf_composite_backward_grad_w: B=%lld", (long long)B);
-  if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward_grad_w: N=%d (1..4096)", N);
-  REQUIRE(B == 0 || (rgb && sigma && z_vals && dsigma && drgb), "nerf_composite_backward_grad_w: null pointer");
   const CompositeAccGrad acc{g_acc, bd, g_w};
-  return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_grad(grad_rgb_map, grad_depth_map),
-                                   &acc, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
+  return dense_stage_grad("nerf_composite_backward_grad_w", rgb, sigma, z_vals, grad_rgb_map, grad_depth_map, B, N,
+                          dsigma, drgb, &acc, stream);
 }
 
 int nerf_composite_merged_backward_w(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
@@ -1101,26 +1112,17 @@ int nerf_composite_merged_backward_w(const float* rgb_c, const float* sigma_c, c
                                      const float* grad_depth_map, int64_t B, int N, int Nf, int accumulate_coarse,
                                      float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f, const float* g_acc,
                                      float bd, const float* g_w, nerf_stream_t stream) {
-  REQUIRE(B >= 0, "nerf_composite_merged_backward_w: B=%lld", (long long)B);
-  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_merged_backward_w: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
-  REQUIRE(B == 0 || (rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c && drgb_c && dsigma_f && drgb_f),
-          "nerf_composite_merged_backward_w: null pointer");
   const CompositeAccGrad acc{g_acc, bd, g_w};
-  return launch_composite_backward(merged_samples(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, B, N, Nf),
-                                   upstream_grad(grad_rgb_map, grad_depth_map), &acc,
-                                   {dsigma_c, drgb_c, dsigma_f, drgb_f, accumulate_coarse}, (hipStream_t)stream);
+  return merged_stage_grad("nerf_composite_merged_backward_w", rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, grad_rgb_map,
+                           grad_depth_map, B, N, Nf, accumulate_coarse, dsigma_c, drgb_c, dsigma_f, drgb_f, &acc, stream);
 }
 
 int nerf_composite_backward_grad_acc(const float* rgb, const float* sigma, const float* z_vals,
                                      const float* grad_rgb_map, const float* grad_depth_map, int64_t B, int N,
                                      float* dsigma, float* drgb, const float* g_acc, float bd, nerf_stream_t stream) {
-  REQUIRE(B >= 0, "nerf_composite_backward_grad_acc: B=%lld", (long long)B);
-  if (N < 1 || N > 4096) return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_backward_grad_acc: N=%d (1..4096)", N);
-  REQUIRE(B == 0 || (rgb && sigma && z_vals && dsigma && drgb), "nerf_composite_backward_grad_acc: null pointer");
   const CompositeAccGrad acc{g_acc, bd};
-  return launch_composite_backward(dense_samples(rgb, sigma, z_vals, B, N), upstream_grad(grad_rgb_map, grad_depth_map),
-                                   &acc, {dsigma, drgb, nullptr, nullptr, 0}, (hipStream_t)stream);
+  return dense_stage_grad("nerf_composite_backward_grad_acc", rgb, sigma, z_vals, grad_rgb_map, grad_depth_map, B, N,
+                          dsigma, drgb, &acc, stream);
 }
 
 int nerf_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c, const float* rgb_f,
@@ -1128,15 +1130,9 @@ int nerf_composite_merged_backward_acc(const float* rgb_c, const float* sigma_c,
                                        const float* grad_rgb_map, const float* grad_depth_map, int64_t B, int N, int Nf,
                                        int accumulate_coarse, float* dsigma_c, float* drgb_c, float* dsigma_f,
                                        float* drgb_f, const float* g_acc, float bd, nerf_stream_t stream) {
-  REQUIRE(B >= 0, "nerf_composite_merged_backward_acc: B=%lld", (long long)B);
-  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_merged_backward_acc: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
-  REQUIRE(B == 0 || (rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c && drgb_c && dsigma_f && drgb_f),
-          "nerf_composite_merged_backward_acc: null pointer");
   const CompositeAccGrad acc{g_acc, bd};
-  return launch_composite_backward(merged_samples(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, B, N, Nf),
-                                   upstream_grad(grad_rgb_map, grad_depth_map), &acc,
-                                   {dsigma_c, drgb_c, dsigma_f, drgb_f, accumulate_coarse}, (hipStream_t)stream);
+  return merged_stage_grad("nerf_composite_merged_backward_acc", rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, grad_rgb_map,
+                           grad_depth_map, B, N, Nf, accumulate_coarse, dsigma_c, drgb_c, dsigma_f, drgb_f, &acc, stream);
 }
 
 int nerf_composite_merged_backward(const float* rgb_c, const float* sigma_c, const float* rgb_f, const float* sigma_f,
@@ -1144,24 +1140,17 @@ int nerf_composite_merged_backward(const float* rgb_c, const float* sigma_c, con
                                    const float* grad_depth_map, int64_t B, int N, int Nf, int accumulate_coarse,
                                    float* dsigma_c, float* drgb_c, float* dsigma_f, float* drgb_f,
                                    nerf_stream_t stream) {
-  REQUIRE(B >= 0, "nerf_composite_merged_backward: B=%lld", (long long)B);
-  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_composite_merged_backward: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
-  REQUIRE(B == 0 || (rgb_c && sigma_c && rgb_f && sigma_f && src && z_all && dsigma_c && drgb_c && dsigma_f && drgb_f),
-          "nerf_composite_merged_backward: null pointer");
-  return launch_composite_backward(merged_samples(rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, B, N, Nf),
-                                   upstream_grad(grad_rgb_map, grad_depth_map), nullptr,
-                                   {dsigma_c, drgb_c, dsigma_f, drgb_f, accumulate_coarse}, (hipStream_t)stream);
+  return merged_stage_grad("nerf_composite_merged_backward", rgb_c, sigma_c, rgb_f, sigma_f, src, z_all, grad_rgb_map,
+                           grad_depth_map, B, N, Nf, accumulate_coarse, dsigma_c, drgb_c, dsigma_f, drgb_f, nullptr,
+                           stream);
 }
 
 int nerf_sample_importance_src(const float* z_vals, const float* weights, int64_t B, int N, int Nf, const float* u_lin,
                                const float* u_rand, uint64_t seed, float* z_all, float* z_fine, uint16_t* merged_src,
                                nerf_stream_t stream) {
-  REQUIRE(B >= 0, "nerf_sample_importance_src: B=%lld", (long long)B);
-  if (N < 1 || N > 256 || Nf < 1 || Nf > 1024)
-    return set_error(NERF_ERR_UNSUPPORTED, "nerf_sample_importance_src: N=%d (1..256) Nf=%d (1..1024)", N, Nf);
-  REQUIRE(B == 0 || (z_vals && weights && u_lin && z_all && z_fine && merged_src),
-          "nerf_sample_importance_src: null pointer");
+  if (int rc = check_merged_stage("nerf_sample_importance_src", B, N, Nf,
+                                  z_vals && weights && u_lin && z_all && z_fine && merged_src))
+    return rc;
   return launch_importance(nullptr, nullptr, z_vals, weights, B, N, Nf, u_lin, u_rand, seed, z_all, nullptr, nullptr,
                            nullptr, nullptr, nullptr, z_fine, nullptr, (hipStream_t)stream, merged_src);
 }

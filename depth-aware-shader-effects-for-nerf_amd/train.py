@@ -160,7 +160,6 @@ class Trainer:
         self.packed = torch.empty(self.lib.nerf_packed_weights_floats(), device=self.dev)
         self.packedT = torch.empty(self.lib.nerf_packed_transposed_floats(), device=self.dev)
         self.dapp = torch.empty(1, _APP_DIM, device=self.dev)
-        self.loss_buf = torch.empty(1, device=self.dev)
         self.lr = config.learning_rate if lr is None else lr
         self.initial_lr = self.lr
         self.betas, self.eps = betas, eps
@@ -169,17 +168,18 @@ class Trainer:
         self._tvals = {}
         self._side = None          # side stream for the transposed packing (forward_backward)
         self._bg_row = None        # the fixed background colour as a (1,3) device tensor
-        if self.hierarchical:
-            # (fine, coarse) mean squared errors; with a background (fine colour, coarse colour, fine
-            # opacity, coarse opacity), with a distortion weight also (fine distortion, coarse distortion)
-            dist = self.distortion_weight > 0.0
-            self._loss4 = torch.zeros(6 if dist else 4, device=self.dev)
-            self.loss_parts = self._loss4 if (dist or self._bg_configured()) else self._loss4[:2]
-            self._ws_hier = None
-        elif self.distortion_weight > 0.0:
-            self.loss_parts = torch.zeros(3, device=self.dev)   # (colour, opacity, distortion)
-        elif self._bg_configured():
-            self.loss_parts = torch.zeros(2, device=self.dev)   # (colour, opacity)
+        # The backward's form, decided once: the suffix of the C entries the steps call, which fixes the loss
+        # terms (colour; "_bg": and opacity; "_dist": and distortion).  Term k of part p (0 fine or the only
+        # one, 1 coarse) of P parts is loss float k * P + p; a plain dense trainer has the one float and no
+        # loss_parts.
+        self.loss_form = "_dist" if self.distortion_weight > 0.0 else "_bg" if self._bg_configured() else ""
+        terms = {"": 1, "_bg": 2, "_dist": 3}[self.loss_form]
+        self._term_weights = (self.acc_weight, self.distortion_weight)[:terms - 1]   # of the terms behind the colour
+        self._parts = 2 if self.hierarchical else 1
+        self._ws_hier = None
+        self._loss = torch.zeros(terms * self._parts, device=self.dev)
+        if terms * self._parts > 1:
+            self.loss_parts = self._loss
         self.occupancy = occupancy
         self.occupancy_refresh = None
         self.live_fraction = None  # share of the last step's samples the grid marked live
@@ -246,15 +246,13 @@ class Trainer:
         return self.background is not None or self.acc_weight > 0.0
 
     def _bg_args(self, B, seed, alpha):
-        """None for a trainer without a background or an opacity term (the original calls; an alpha is
-        refused there); else the _bg backward's (alpha, bg, bg_rows, acc_weight, rgb_final).  A trainer with
-        only a distortion weight gets them with every option off."""
+        """The step's (alpha, bg, bg_rows, rgb_final) tensors for the _bg and _dist entries: every option
+        off for a trainer with only a distortion weight, and no rgb_final for the plain form (which passes
+        none of them).  An alpha is refused without a background or an opacity term."""
         if not self._bg_configured():
             if alpha is not None:
                 raise ValueError("Trainer: alpha belongs to a trainer with background= or acc_weight > 0")
-            if self.distortion_weight > 0.0:
-                return None, None, 0, 0.0, torch.empty(B, 3, device=self.dev)
-            return None
+            return None, None, 0, torch.empty(B, 3, device=self.dev) if self.loss_form else None
         if alpha is not None:
             alpha = alpha.reshape(-1).to(self.dev, torch.float32).contiguous()
             if alpha.shape[0] != B:
@@ -266,7 +264,7 @@ class Trainer:
             if self._bg_row is None:
                 self._bg_row = torch.tensor([self.background], dtype=torch.float32, device=self.dev)
             bg, rows = self._bg_row, 1
-        return alpha, bg, rows, float(self.acc_weight), torch.empty(B, 3, device=self.dev)
+        return alpha, bg, rows, torch.empty(B, 3, device=self.dev)
 
     def validation_background(self):
         """The fixed colour a validation render composites over: the trainer's, white for "random"."""
@@ -287,39 +285,31 @@ class Trainer:
         self._pack_transposed_aside(main)
         return self._maps(B) + self._app_row(app_idx)
 
-    def _backward(self, main, entry, args, ws, app_idx, rgb_map, bgo, hier=False):
-        """The step variants' epilogue: the join with the transposed packing, then the C entry `entry`
-        (`args`: what it takes between packedT and the gradient pointers, ending in app, rows) or, for a
-        trainer with a background, its _bg twin with `bgo` appended; with a distortion weight its _dist twin
-        with the weight, near and far behind those.  (loss, the map the loss was taken on)"""
+    def _backward(self, main, entry, args, ws, app_idx, rgb_map, bgo):
+        """The step variants' epilogue: the join with the transposed packing, then the C entry `entry` in
+        the trainer's form (`args`: what it takes between packedT and the gradient pointers, ending in app,
+        rows): the _bg form with `bgo` (_bg_args) and the opacity weight behind ws_bytes, the _dist form
+        with the distortion weight, near and far behind those.  (loss, the map the loss was taken on)"""
         P, rows = _lib.ptr, args[-1]
         # d app of the batch's image goes straight into its row of the table's gradient
         dapp = self.app_grad[int(app_idx)] if rows else None
         main.wait_event(self._join)
-        if bgo is None:
-            lp = self.loss_parts if hier else self.loss_buf
-            tail, out = (), rgb_map
-        else:
-            al, bg, bg_rows, aw, out = bgo
-            dw = self.distortion_weight
-            entry, lp = entry + ("_dist" if dw > 0.0 else "_bg"), self.loss_parts
-            tail = (P(al), P(bg), bg_rows, aw, P(out)) + ((None,) if hier else ())     # (no coarse_final)
-            if dw > 0.0:
-                tail += (dw, self.near, self.far)
+        al, bg, bg_rows, out = bgo
+        tail = ()
+        if self.loss_form:
+            tail = (P(al), P(bg), bg_rows, self.acc_weight, P(out)) + (None,) * (self._parts - 1)   # (no coarse_final)
+        if self.loss_form == "_dist":
+            tail += (self.distortion_weight, self.near, self.far)
+        lp, n, entry = self._loss, self._parts, entry + self.loss_form
         _lib.check(getattr(self.lib, entry)(P(self.packed), P(self.packedT), *args, self.grad_ptrs, P(dapp), P(lp),
                                             P(ws), ws.numel(), *tail, _lib.stream()), entry)
         self._zero_unused_projection(rows)
-        # loss_parts: (colour, opacity), hierarchical (fine colour, coarse colour, fine opacity, coarse opacity)
-        if bgo is None:
-            return (lp[0] + self.coarse_loss_weight * lp[1] if hier else lp[0]), out
-        # ... then with a distortion weight the distortion part(s): total = (colour + aw opacity) + dw distortion
-        if hier:
-            fine, coarse = lp[0] + aw * lp[2], lp[1] + aw * lp[3]
-            if dw > 0.0:
-                fine, coarse = fine + dw * lp[4], coarse + dw * lp[5]
-            return fine + self.coarse_loss_weight * coarse, out
-        total = lp[0] + aw * lp[1]
-        return (total + dw * lp[2] if dw > 0.0 else total), out
+        # per part ((colour + acc_weight opacity) + distortion_weight distortion), then fine + weight coarse
+        total = [lp[p] for p in range(n)]
+        for k, weight in enumerate(self._term_weights, 1):
+            total = [t + weight * lp[k * n + p] for p, t in enumerate(total)]
+        loss = total[0] + self.coarse_loss_weight * total[1] if n == 2 else total[0]
+        return loss, (rgb_map if out is None else out)
 
     # ------------------------------------------------------------------------------ one step
     def forward_backward(self, rays_o, rays_d, target, app_idx=None, *, t_rand=None, u_rand=None, seed=None,
@@ -359,7 +349,7 @@ class Trainer:
         return self._backward(main, "nerf_train_backward", (P(rgb_map), P(tgt), B, N, P(app), rows), ws, app_idx,
                               rgb_map, bgo)
 
-    def _forward_backward_hier(self, o, d, tgt, app_idx, t_rand, u_rand, seed, _marks=None, bgo=None):
+    def _forward_backward_hier(self, o, d, tgt, app_idx, t_rand, u_rand, seed, _marks, bgo):
         """forward_backward with the fine pass: nerf_train_hier_forward + nerf_train_hier_backward on one
         workspace that carries both sample sets' saves."""
         lib, s, P = self.lib, _lib.stream(), _lib.ptr
@@ -388,9 +378,9 @@ class Trainer:
             _marks[1].record(main)
         return self._backward(main, "nerf_train_hier_backward",
                               (P(rgb_map), P(rgb_c), P(tgt), B, N, Nf, self.coarse_loss_weight, P(app), rows), ws, app_idx,
-                              rgb_map, bgo, hier=True)
+                              rgb_map, bgo)
 
-    def _forward_backward_occ(self, o, d, tgt, app_idx, t_rand, seed, _marks=None, bgo=None):
+    def _forward_backward_occ(self, o, d, tgt, app_idx, t_rand, seed, _marks, bgo):
         """forward_backward on the live samples of self.occupancy: sample + classify, the live count
         to pinned host memory behind an event, the two weight packings (which cover that copy), the
         wait, then the gathered forward and the compact backward."""
@@ -723,7 +713,7 @@ def train_nerf(config, dataset, save_dir="checkpoints", group=None, num_iteratio
         if i % config.scheduler_step_size == 0:                          # StepLR, train.py:95-96
             trainer.lr *= config.scheduler_gamma
         # the fine MSE; with a background or an opacity term the (fine) colour term
-        loss_v = float(trainer.loss_parts[0]) if (trainer.hierarchical or bg_kwargs or dist_kwargs) else float(loss)
+        loss_v = float(trainer.loss_parts[0]) if (trainer.hierarchical or trainer.loss_form) else float(loss)
         psnr_v = -10.0 * math.log10(loss_v) if loss_v > 0 else float("inf")
         losses.append(loss_v)
         psnrs.append(psnr_v)

@@ -225,6 +225,7 @@ class _StubTrainer:
         self.kw, self.steps_seen = kw, []
         self.rank, self.lr, self.hierarchical, self.n_importance = 0, 1e-3, False, None
         self.loss_parts = torch.tensor([0.25, 0.5])
+        self.loss_form = "_bg" if "background" in kw else ""      # as Trainer decides it from its arguments
         self.model = object()
         _StubTrainer.made.append(self)
 

@@ -226,6 +226,71 @@ def error_cases(lib):
            ("app_rows = 2", dict(app_rows=2)), ("coarse_weight = -1", dict(coarse_weight=-1.0)),
            ("gradient 3 null", dict(grads=grads_hole)), ("workspace one byte short", {}),
            ("no forward wrote the workspace", dict(ws_bytes=ws_bytes))] + bg_loss)
+
+    # ---- the hierarchical step itself
+    hier_shape = [("B = -1", dict(B=-1)), ("N = 1", dict(N=1)), ("N = 257", dict(N=257)), ("Nf = 0", dict(Nf=0)),
+                  ("Nf = 1025", dict(Nf=1025)), ("B = 0", dict(B=0)), ("2^31 coarse samples", dict(B=1 << 23, N=256)),
+                  ("app_rows = 2", dict(app_rows=2))]
+    hier_step = hier_shape + [("coarse_weight = -1", dict(coarse_weight=-1.0)),
+                              ("gradient 3 null", dict(grads=grads_hole)), ("workspace one byte short", {}),
+                              ("no forward wrote the workspace", dict(ws_bytes=ws_bytes))]
+    order = ["packed", "rays_o", "rays_d", "B", "near", "far", "N", "Nf", "t_vals", "u_lin", "perturb", "t_rand",
+             "u_rand", "seed", "app", "app_rows", "rgb_map", "depth_map", "weights_out", "z_out", "coarse_rgb",
+             "coarse_depth", "coarse_weights", "workspace", "ws_bytes", "stream"]
+    fwd = dict(packed=P, rays_o=P, rays_d=P, B=B, near=2.0, far=6.0, N=N, Nf=NF, t_vals=P, u_lin=P, perturb=1, t_rand=P,
+               u_rand=P, seed=7, app=P, app_rows=1, rgb_map=P, depth_map=P, weights_out=P, z_out=P, coarse_rgb=P,
+               coarse_depth=P, coarse_weights=P, workspace=0x600000, ws_bytes=ws_bytes - 1, stream=None)
+    sweep("nerf_train_hier_forward", order, fwd,
+          ["packed", "rays_o", "rays_d", "t_vals", "u_lin", "app", "rgb_map", "depth_map", "coarse_rgb", "coarse_depth",
+           "workspace"], hier_shape + [("workspace one byte short", {})])
+    hier = ["packed", "packedT", "rgb_map", "coarse_rgb", "target", "B", "N", "Nf", "coarse_weight", "app", "app_rows",
+            "grads", "dapp", "loss", "workspace", "ws_bytes"]
+    base = dict(base, workspace=0x700000)
+    sweep("nerf_train_hier_backward", hier + ["stream"], base, backward_ptrs + ["coarse_rgb"], hier_step)
+
+    # ---- the backward steps with the distortion term
+    dist_loss = bg_loss + [("dist_weight = -1", dict(dist_weight=-1.0)), ("dist_weight NaN", dict(dist_weight=float("nan"))),
+                           ("far <= near", dict(near=6.0, far=2.0)), ("far infinite", dict(far=float("inf")))]
+    dist_tail = ["dist_weight", "near", "far", "stream"]
+    base = dict(base, dist_weight=0.01, near=2.0, far=6.0, workspace=0x800000)
+    sweep("nerf_train_hier_backward_dist", hier + bg_tail[:-1] + ["coarse_final"] + dist_tail, base,
+          backward_ptrs + ["coarse_rgb"], hier_step + dist_loss)
+    ws_bytes = lib.nerf_train_workspace_bytes(B, N)
+    base = dict(base, workspace=0x900000, ws_bytes=ws_bytes - 1)
+    sweep("nerf_train_backward_dist", step + bg_tail[:-1] + dist_tail, base, backward_ptrs,
+          shape + dist_loss + [("app_rows = 2", dict(app_rows=2)), ("gradient 3 null", dict(grads=grads_hole)),
+                               ("workspace one byte short", {}),
+                               ("no forward wrote the workspace", dict(ws_bytes=ws_bytes))])
+    ws_bytes = lib.nerf_train_occ_workspace_bytes(B, N)
+    base = dict(base, workspace=0xA00000, ws_bytes=ws_bytes - 1)
+    sweep("nerf_train_occ_backward_dist", step[:i] + ["M_live"] + step[i:] + bg_tail[:-1] + dist_tail, base,
+          backward_ptrs, occ_step + dist_loss + [("gradient 3 null", dict(grads=grads_hole)),
+                                                 ("no forward with this M_live wrote the workspace",
+                                                  dict(ws_bytes=ws_bytes))], f32_only=True)
+
+    # ---- the distortion stage (no workspace either)
+    order = ["rgb", "sigma", "z_vals", "grad_rgb_map", "grad_depth_map", "B", "N", "dsigma", "drgb", "g_acc", "bd", "g_w",
+             "stream"]
+    sweep("nerf_composite_backward_grad_w", order,
+          dict(rgb=P, sigma=P, z_vals=P, grad_rgb_map=P, grad_depth_map=P, B=B, N=N, dsigma=P, drgb=P, g_acc=P, bd=6.0,
+               g_w=P, stream=None), ["rgb", "sigma", "z_vals", "dsigma", "drgb"], shape)
+    order = ["rgb_c", "sigma_c", "rgb_f", "sigma_f", "src", "z_all", "grad_rgb_map", "grad_depth_map", "B", "N", "Nf",
+             "accumulate", "dsigma_c", "drgb_c", "dsigma_f", "drgb_f", "g_acc", "bd", "g_w", "stream"]
+    sweep("nerf_composite_merged_backward_w", order,
+          dict(rgb_c=P, sigma_c=P, rgb_f=P, sigma_f=P, src=P, z_all=P, grad_rgb_map=P, grad_depth_map=P, B=B, N=N, Nf=NF,
+               accumulate=1, dsigma_c=P, drgb_c=P, dsigma_f=P, drgb_f=P, g_acc=P, bd=6.0, g_w=P, stream=None),
+          ["rgb_c", "sigma_c", "rgb_f", "sigma_f", "src", "z_all", "dsigma_c", "drgb_c", "dsigma_f", "drgb_f"], merged)
+    order = ["weights", "z_vals", "B", "T", "near", "far", "scale", "loss_rays", "g_w", "stream"]
+    sweep("nerf_distortion", order,
+          dict(weights=P, z_vals=P, B=B, T=N, near=2.0, far=6.0, scale=1.0, loss_rays=P, g_w=P, stream=None),
+          ["weights", "z_vals"],
+          [("B = -1", dict(B=-1)), ("T = 0", dict(T=0)), ("T = 4097", dict(T=4097)), ("B = 0", dict(B=0)),
+           ("far <= near", dict(near=6.0, far=2.0)), ("far infinite", dict(far=float("inf"))),
+           ("scale NaN", dict(scale=float("nan"))), ("scale infinite", dict(scale=float("inf")))])
+    order = ["z_vals", "weights", "B", "N", "Nf", "u_lin", "u_rand", "seed", "z_all", "z_fine", "merged_src", "stream"]
+    sweep("nerf_sample_importance_src", order,
+          dict(z_vals=P, weights=P, B=B, N=N, Nf=NF, u_lin=P, u_rand=P, seed=7, z_all=P, z_fine=P, merged_src=P,
+               stream=None), ["z_vals", "weights", "u_lin", "z_all", "z_fine", "merged_src"], merged)
     return out
 
 
@@ -259,7 +324,7 @@ def test_error_parity_with_the_recording():
     for k, (rc, msg) in want.items():
         assert rc != 2, k
         assert (rc == 0) == k.endswith((": B = 0", ": R = 0", ": M = 0")), k
-    assert len(want) >= 327
+    assert len(want) >= 497
 
 
 if __name__ == "__main__":
