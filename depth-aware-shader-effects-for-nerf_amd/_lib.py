@@ -189,6 +189,15 @@ _SIGNATURES = {
     "nerf_train_hier_backward_dist": (ctypes.c_int, _HIER_STEP + _BG + [_V] + _DIST + [_V]),
     "nerf_composite_backward_grad_w": (ctypes.c_int, _STAGE + _ACC + [_V, _V]),
     "nerf_composite_merged_backward_w": (ctypes.c_int, _MERGED_STAGE + _ACC + [_V, _V]),
+    # position gradient and normals (include/nerfmi_train.h)
+    "nerf_packed_input_floats": (ctypes.c_size_t, []),
+    "nerf_pack_weights_input": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _V, _V]),
+    "nerf_pack_weights_input_host": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _V]),
+    "nerf_mlp_position_grad": (ctypes.c_int, [_V, _V, _V, _I64, _V, _V]),
+    "nerf_composite_normals": (ctypes.c_int, [_V, _V, _I64, ctypes.c_int, _V, _V]),
+    "nerf_render_normals_workspace_bytes": (ctypes.c_size_t, [_I64, ctypes.c_int]),
+    "nerf_render_normals": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _I64, ctypes.c_int, _V, _V, ctypes.c_size_t,
+                                           _V]),
     # depth-aware post effects (include/nerfmi.h)
     "nerf_effect_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "nerf_depth_normalize": (ctypes.c_int, [_V, _I64, _V, _V, ctypes.c_size_t, _V]),

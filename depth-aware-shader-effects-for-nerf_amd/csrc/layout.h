@@ -285,6 +285,39 @@ static_assert(kSaveRow % 8 == 0 && kGradRow % 8 == 0 && kSaveEncX % 8 == 0 && kS
                   kGradRgb % 8 == 0,
               "every slice of the tile-major rows starts on a feature group");
 
+// ---- input-gradient weights (nerf_pack_weights_input; packer and reader in normals.hip) ----------
+// The position gradient's one GEMM, g_enc = W_0^T dpre_0 + W_4[:, 256:319]^T dpre_4, as a 64 x 512
+// operand of v_mfma_f32_32x32x2_f32: output rows are encoding features (63 + a zero row), the 512
+// inputs k are the neurons of dpre_0 (k < 256) and dpre_4 (k >= 256).  A buffer of its own.
+//
+// k order: the gradient rows are tile-major, so lane l = 32 h + s reads, for input group G (8 inputs),
+// the 16 bytes at floats s 8 + 4 h of the group: inputs 8 G + 4 h + j, j = 0..3, as they lie; they are
+// the B operands of MFMA k-steps 4 G + j.  A fragment block is (output tile t, group G): 64 lanes x 4
+// floats, lane l holding W_in[row(t, l & 31)][8 G + 4 (l >> 5) + j].
+//
+// Output-row order: the accumulator leaves, in lane half h, value i = 16 t + g (tile t, register g) =
+// tile row (g & 3) + 8 (g >> 2) + 4 h.  Values 2 j and 2 j + 1 (j = 0..14) are the sin and the cos row
+// of frequency level 2 (j / 3) + h, component j % 3: a lane holds both partners of its 15 (level,
+// component) pairs, even levels in half 0 and odd levels in half 1.  Value 30 is the identity row of
+// component h, value 31 that of component 2 in half 0 and the zero row in half 1.
+constexpr int kInGroups = 2 * kHidden / 8;                           // 64 input groups
+constexpr size_t kPackedInFloats = (size_t)2 * kInGroups * 64 * 4;   // 32768 floats = 128 KiB
+// Encoding feature (reference order) of value i (0..31) of lane half h, or -1 for the zero row.
+NERF_HD inline int in_out_feature(int i, int h) {
+  if (i < 30) {
+    const int j = i >> 1, level = 2 * (j / 3) + h, c = j % 3;
+    return 3 + 6 * level + c + 3 * (i & 1);
+  }
+  if (i == 30) return h;
+  return h ? -1 : 2;
+}
+// ... of tile row r (the A operand's lane & 31) of output tile t
+NERF_HD inline int in_row_feature(int t, int r) { return in_out_feature(16 * t + (r & 3) + 4 * (r >> 3), (r >> 2) & 1); }
+// Gradient-row feature of input k: dpre_0's neuron k, or dpre_4's neuron k - 256.
+NERF_HD inline int in_grad_feature(int k) { return k < kHidden ? k : kSkipLayer * kHidden + (k - kHidden); }
+// Float offset of element j of lane `lane` in fragment block (tile t, group G).
+NERF_HD inline size_t in_elem(int t, int G, int lane, int j) { return ((size_t)(t * kInGroups + G) * 64 + lane) * 4 + j; }
+
 // Float offset, inside matrix m's fragment array, of element j of lane `lane` in the
 // fragment block (n-tile nt, k-step quad kq): ks = 4*kq + j.
 NERF_HD inline size_t frag_elem(int m, int nt, int kq, int lane, int j) {

@@ -56,16 +56,21 @@ def shard_rays(ray_fn, H, W, n_frames, start, end):
 def _render_shard(ray_fn, render_fn, H, W, n_frames, start, end, buf):
     if end > start:
         o, d = shard_rays(ray_fn, H, W, n_frames, start, end)
-        rgb, depth, *acc = render_fn(o, d, start)
+        rgb, depth, *more = render_fn(o, d, start)
         buf[: end - start, :3] = rgb.to(buf.device)
         buf[: end - start, 3:4] = depth.reshape(-1, 1).to(buf.device)
-        if buf.shape[1] > 4:       # the opacity map travels beside the depth
-            buf[: end - start, 4:] = acc[0].reshape(-1, 1).to(buf.device)
+        at = 4                     # the opacity map (one column), then the normal map (three), beside the depth
+        for m in more:
+            if at >= buf.shape[1]:
+                break
+            m = m.reshape(end - start, -1)
+            buf[: end - start, at:at + m.shape[1]] = m.to(buf.device)
+            at += m.shape[1]
 
 
 @torch.no_grad()
 def render_frames_sharded(ray_fn, render_fn, H, W, n_frames, group=None, device=None, virtual_shards=None,
-                          with_acc=False):
+                          with_acc=False, with_normals=False):
     """Render n_frames HxW frames over the ranks of `group`.
 
     ray_fn(frame, row0, nrows) -> (rays_o, rays_d) for those rows (row-major, (nrows*W, 3));
@@ -77,13 +82,15 @@ def render_frames_sharded(ray_fn, render_fn, H, W, n_frames, group=None, device=
     check of the sharding and reassembly of a G-GPU run).
     with_acc: render_fn returns (rgb, depth, acc (n,1)) and the opacity map is gathered like the depth:
     the result is then (rgb, depth, acc (n_frames,H,W)).
+    with_normals: render_fn returns a normal map (n,3) after whatever it returns otherwise; it is gathered as
+    three more columns and the result gains a (n_frames,H,W,3) tensor at its end.
     Returns (rgb (n_frames,H,W,3), depth (n_frames,H,W)) on every rank.  Inference only (no autograd
     graph: the outputs are copied into the reassembly buffer, as the reference renders its frames
     under torch.no_grad(), run.py:217).
     """
     world, rank, collective = _world(group)
     total = n_frames * H * W
-    C = 5 if with_acc else 4
+    C = 4 + (1 if with_acc else 0) + (3 if with_normals else 0)
     if virtual_shards is not None:
         if world != 1:
             raise ValueError("render_frames_sharded: virtual_shards runs in one process (world size 1)")
@@ -103,15 +110,15 @@ def render_frames_sharded(ray_fn, render_fn, H, W, n_frames, group=None, device=
         else:
             out = buf
     frames = out[:total].reshape(n_frames, H, W, C)
-    if with_acc:
-        return frames[..., :3], frames[..., 3], frames[..., 4]
-    return frames[..., :3], frames[..., 3]
+    res = (frames[..., :3], frames[..., 3]) + ((frames[..., 4],) if with_acc else ())
+    return res + ((frames[..., C - 3:],) if with_normals else ())
 
 
 @torch.no_grad()
 def render_path_frames(model, poses, H, W, focal, near, far, n_samples, n_importance=0, appearance_embedding=None,
                        perturb=False, hierarchical=False, seed=0, group=None, timing=None, virtual_shards=None,
-                       occupancy=None, background=None, background_depth=None, return_acc=False):
+                       occupancy=None, background=None, background_depth=None, return_acc=False,
+                       return_normals=False):
     """render_frames_sharded with nerfmi's HIP get_rays / render_rays (one list entry per frame:
     a (3,4)/(4,4) c2w, kept on the host: ray generation takes the pose by value, so no shard
     synchronises on a device-to-host copy).  The in-kernel draws are keyed by `seed` and the global
@@ -119,7 +126,8 @@ def render_path_frames(model, poses, H, W, focal, near, far, n_samples, n_import
     render_rays (per-launch MLP events); occupancy: an OccupancyGrid, passed to render_rays.
     background (three floats, or one colour per ray of the whole batch of frames, (n_frames*H*W, 3)),
     background_depth and return_acc go to render_rays with every shard; with return_acc the result is
-    (rgb, depth, acc (n_frames,H,W)), the opacity map gathered like the depth."""
+    (rgb, depth, acc (n_frames,H,W)), the opacity map gathered like the depth.  return_normals: render_rays'
+    normal map is gathered too and the result gains a (n_frames,H,W,3) tensor at its end."""
     from . import _lib
     from .ray_utils import rays_on_device
     from .render import render_rays
@@ -142,11 +150,15 @@ def render_path_frames(model, poses, H, W, focal, near, far, n_samples, n_import
             extra["background_depth"] = background_depth
         if return_acc:
             extra["return_acc"] = True
+        if return_normals:
+            extra["return_normals"] = True
         rgb, depth, ex = render_rays(model, o, d, near, far, n_samples, n_importance,
                                      appearance_embedding=appearance_embedding, perturb=perturb,
                                      hierarchical=hierarchical, seed=int(seed) & (2 ** 62 - 1), ray_offset=offset,
                                      timing=timing, **extra)
-        return (rgb, depth, ex["acc_map"]) if return_acc else (rgb, depth)
+        res = (rgb, depth, ex["acc_map"]) if return_acc else (rgb, depth)
+        return res + ((ex["normal_map"],) if return_normals else ())
 
     return render_frames_sharded(ray_fn, render_fn, H, W, len(c2ws), group=group, device=dev,
-                                 virtual_shards=virtual_shards, **({"with_acc": True} if return_acc else {}))
+                                 virtual_shards=virtual_shards, **({"with_acc": True} if return_acc else {}),
+                                 **({"with_normals": True} if return_normals else {}))

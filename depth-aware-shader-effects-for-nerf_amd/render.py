@@ -41,6 +41,14 @@ and ``background_color``.  Keyword-only extras:
                       (nerf_render_rays_bg / nerf_render_rays_occ_bg), and under gradients on the
                       coarse differentiable path, where acc_map carries a gradient too
                       (nerf_composite_backward_grad_acc); staged=True and timing= take none of them.
+  return_normals      extras['normal_map'] (...,3) = sum w_i n_i over the returned sample set and weights
+                      (with hierarchical=True the merged set and the fine weights), n_i the normalised
+                      negative density gradient at the sample (normals.py): world space,
+                      pointing out of the surface, not renormalised, unaffected by a background.  A second
+                      pass behind the render (nerf_render_normals): every other output is bit for bit
+                      what the call returns without it.  Works plain, hierarchical, with occupancy= and
+                      background=, and chunked; not differentiable: with gradients enabled on a trainable
+                      model, staged=True or timing= it raises ValueError.
 ``render_rays`` is the same function (the north-star name).
 
 With gradients enabled and a trainable model (or an appearance embedding that requires grad),
@@ -77,9 +85,17 @@ def packed_for(model):
 def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, appearance_embedding=None,
                   background_color=None, perturb=True, *, hierarchical=False, t_rand=None, u_rand=None,
                   seed=None, ray_offset=0, timing=None, staged=False, reuse_coarse=True, occupancy=None,
-                  background=None, background_depth=None, return_acc=False):
+                  background=None, background_depth=None, return_acc=False, return_normals=False):
     from . import autograd
     bg_on = background is not None or background_depth is not None or bool(return_acc)
+    if return_normals:
+        if staged or timing is not None:
+            raise ValueError(f"nerfmi.volume_render({'staged=True' if staged else 'timing='}) takes no "
+                             f"return_normals=: the normal map runs behind the single-call path")
+        if autograd.needs_grad(model, appearance_embedding if uses_appearance(model) else None, rays_o, rays_d):
+            raise ValueError("nerfmi.volume_render(return_normals=True) with gradients enabled: the normal map is "
+                             "not differentiable (render under torch.no_grad(), or with parameters that do not "
+                             "require grad)")
     if bg_on and (staged or timing is not None):
         raise ValueError(f"nerfmi.volume_render({'staged=True' if staged else 'timing='}) takes no background=, "
                          f"background_depth= or return_acc=: they run on the single-call path")
@@ -167,6 +183,12 @@ def volume_render(model, rays_o, rays_d, near, far, n_samples, n_importance, app
                          int(ray_offset), app, rows, rgb_map, depth_map, weights, z_vals, crgb if Nf else None,
                          cdepth if Nf else None, timing, reuse_coarse)
     out = rays_o.device
+    if return_normals:    # the density-gradient pass on the sample set and weights just returned (normals.py)
+        from .normals import render_normals
+        dn = torch.empty_like(d)
+        _lib.check(lib.nerf_normalize_dirs(_lib.ptr(d), B, _lib.ptr(dn), _lib.stream()), "nerf_normalize_dirs")
+        extras["normal_map"] = render_normals(model, o, dn, z_vals, weights.reshape(B, T)).reshape(
+            *orig_shape[:-1], 3).to(out)
     if T == 1:   # the reference's per-sample tensors are empty at one sample (render.py:56-58)
         weights = weights[:, :0]
     extras["weights"] = weights.to(out)

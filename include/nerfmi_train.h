@@ -344,6 +344,52 @@ int nerf_wgrad(const float* a, int64_t lda, int N, const float* x, int64_t ldx, 
 int nerf_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
               double lr, double beta1, double beta2, double eps, int64_t step, nerf_stream_t stream);
 
+/* ------------------------------------------------ position gradient and normals
+ * (not reference features; additions to ABI 11)
+ *
+ * Position gradient.  For a sample with position x (the forward's o + d*z, as rounded there), save row S
+ * and gradient row G:
+ *   g_enc[f] = sum_n W0[n][f] dpre_0[n] + sum_n W4[n][256+f] dpre_4[n]          f = 0..62
+ * with W0 = pts_linears.0.weight (256 x 63) and W4 = pts_linears.4.weight (256 x 319, columns 256..318
+ * the skip's encoding part); features in the reference order [x, sin x, cos x, sin 2x, cos 2x, ...] in
+ * blocks of 3; and for component c
+ *   dx[c] = g_enc[c] + sum_{k=0..9} 2^k ( cos(2^k x_c) g_enc[3+6k+c] - sin(2^k x_c) g_enc[6+6k+c] )
+ * The sines and cosines are the saved enc_x values of S (no second trigonometric evaluation; 2^k is an
+ * exact scaling).  Slot 63 of enc_x is not data (under f16x3 it holds a block-exponent record) and is
+ * never read as a feature.  dx is d loss / d x for whatever (dsigma, drgb) nerf_mlp_backward was given.
+ *
+ * Density gradient: the same with dsigma = 1, drgb = 0: the gradient of sigma, exactly 0 where
+ * sigma = 0 (the chain's density-head mask is sigma > 0).
+ * Normal of a sample: n = -g / sqrt(g.g + 1e-30) with g the density gradient; g = 0 gives n = 0.
+ * Normal map: normal_map = sum_i w_i n_i over the sample set and weights a render returned (with a fine
+ * pass: the merged set and the fine weights).  World space, pointing out of the surface, NOT
+ * renormalised: its length is at most the ray's opacity, and a short vector means the weights straddle
+ * disagreeing normals.  A dead sample of an occupancy grid has weight exactly 0 and adds nothing. */
+/* W0^T and W4[:,256:319]^T as one 64 x 512 MFMA operand (row 63 zero), a buffer of its own
+ * (csrc/layout.h "input-gradient weights"). */
+size_t nerf_packed_input_floats(void);
+int nerf_pack_weights_input(const float* const* params, float* packedIn, nerf_stream_t stream);
+int nerf_pack_weights_input_host(const float* const* params, float* packedIn);
+/* dx (M,3) from the tile-major save rows of nerf_mlp_forward_train and gradient rows of nerf_mlp_backward
+ * (either arithmetic: only the f32 rows are read).  Rows past M store nothing. */
+int nerf_mlp_position_grad(const float* packedIn, const float* save, const float* grad, int64_t M,
+                           float* dx, nerf_stream_t stream);
+/* normal_map (B,3) = sum_i weights[r][i] n(dx[r][i]) over dx (B,T,3) and weights (B,T), in double, each
+ * component rounded once, in a fixed order: a ray's result does not depend on the launch's size.
+ * T in 1..4096 (else NERF_ERR_UNSUPPORTED). */
+int nerf_composite_normals(const float* dx, const float* weights, int64_t B, int T, float* normal_map,
+                           nerf_stream_t stream);
+/* The normal map of rays a render returned z_vals (B,T) and weights (B,T) for: per chunk of rays (at
+ * most 2^18 samples, lowered further by the library's launch limit) nerf_ray_features_train without
+ * appearance, nerf_mlp_forward_train on the given z_vals, nerf_mlp_backward with dsigma = 1 and drgb = 0,
+ * nerf_mlp_position_grad, nerf_composite_normals.  rays_d_normalised as nerf_normalize_dirs returns them.
+ * The workspace holds one chunk (0 bytes for refused shapes).  T in 1..4096. */
+size_t nerf_render_normals_workspace_bytes(int64_t B, int T);
+int nerf_render_normals(const float* packed, const float* packedT, const float* packedIn,
+                        const float* rays_o, const float* rays_d_normalised, const float* z_vals,
+                        const float* weights, int64_t B, int T, float* normal_map, void* workspace,
+                        size_t ws_bytes, nerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

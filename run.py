@@ -13,7 +13,8 @@ Added flags: --random_init SEED renders a seeded random-init model when no check
 ignores n_importance, render.py:83-86) with --n_importance samples; --chunk renders the frame
 in ray chunks (0 = whole frame per call); --occupancy RES builds an occupancy grid of RES^3 cells over
 [-X, X]^3 (--occupancy_bound X, default 1.5) from the loaded model once and skips the samples outside
-its set cells in every frame (nerfmi.OccupancyGrid; not a reference feature); in --mode train the
+its set cells in every frame (nerfmi.OccupancyGrid; not a reference feature); --save_normals writes the
+density-gradient normal map normal_{i:03d}.png of every frame beside the depth (render modes); in --mode train the
 same two flags train on the live samples of a RES^3 grid over that box, which the trainer keeps
 current from its own model (all ones for the first 256 steps, then rebuilt every 256 steps), and the
 checkpoints carry the grid; --mode train --hierarchical [--n_importance K] trains with the fine pass on
@@ -95,7 +96,11 @@ def parse_args(argv=None):
                    help='weight of the distortion loss on the ray weights: fewer floaters and less haze in the '
                         'depth map (train mode)')
     p.add_argument('--save_acc', action='store_true', help='write the opacity map acc_*.png beside the depth (render modes only)')
+    p.add_argument('--save_normals', action='store_true',
+                   help='write the density-gradient normal map normal_*.png beside the depth (render modes only)')
     args = p.parse_args(argv)
+    if args.mode == 'train' and args.save_normals:
+        p.error("--save_normals belongs to the render modes (training writes no normal map)")
     if args.mode == 'train' and args.hierarchical and args.occupancy:
         p.error("--hierarchical and --occupancy are not combined in --mode train (the hierarchical step runs on "
                 "every sample)")
@@ -161,10 +166,12 @@ class SceneInfo:
 def render_path(model, scene, config, output_dir, num_frames=120, quality='high', width=800, height=800,
                 start_frame=0, end_frame=None, save_depth=False, raw_output=False, camera_path='circle',
                 spiral_loops=2.0, height_range=(-0.5, 0.5), hierarchical=False, n_importance=None, chunk=0,
-                seed=0, shader=None, occupancy=None, background=None, background_depth=None, save_acc=False):
+                seed=0, shader=None, occupancy=None, background=None, background_depth=None, save_acc=False,
+                save_normals=False):
     """run.py:63-282 (render mode) on nerfmi.  background (three floats), background_depth ('far' = the
     scene's far plane, or a value) and save_acc are nerfmi's: with a background depth the
-    depth-aware effects read a depth that puts empty rays at that depth instead of 0."""
+    depth-aware effects read a depth that puts empty rays at that depth instead of 0.  save_normals
+     writes the density-gradient normal map of every frame beside the depth."""
     import torch.distributed as dist
     from nerfmi import cameras, frames
     from nerfmi.render import render_rays
@@ -197,11 +204,16 @@ def render_path(model, scene, config, output_dir, num_frames=120, quality='high'
             kw["background_depth"] = float(scene.far) if background_depth == 'far' else float(background_depth)
         if save_acc:
             kw["return_acc"] = True
-        acc = None
+        if save_normals:
+            kw["return_normals"] = True
+        acc = normals = None
         if world > 1 or not chunk:
-            rgb, depth, *acc = frames.render_path_frames(model, [c2w], height, width, focal, scene.near, scene.far,
-                                                         n_samples, n_imp, seed=seed + frame_idx, **kw)
-            rgb, depth, acc = rgb[0], depth[0], (acc[0][0] if acc else None)
+            rgb, depth, *more = frames.render_path_frames(model, [c2w], height, width, focal, scene.near, scene.far,
+                                                          n_samples, n_imp, seed=seed + frame_idx, **kw)
+            rgb, depth = rgb[0], depth[0]
+            if save_normals:
+                normals = more.pop()[0]
+            acc = more[0][0] if more else None
         else:
             from nerfmi import get_rays
             o, d = get_rays(height, width, focal, c2w.cuda())
@@ -213,11 +225,15 @@ def render_path(model, scene, config, output_dir, num_frames=120, quality='high'
             depth = torch.cat([dd for _, dd, _ in outs]).reshape(height, width)
             if save_acc:
                 acc = torch.cat([ex["acc_map"] for _, _, ex in outs]).reshape(height, width)
+            if save_normals:
+                normals = torch.cat([ex["normal_map"] for _, _, ex in outs]).reshape(height, width, 3)
         if rank != 0:
             continue
         write_frame(output_dir, frame_idx, rgb, depth, save_depth, raw_output, shader)
         if acc is not None:
             write_acc(output_dir, frame_idx, acc)
+        if normals is not None:
+            write_normals(output_dir, frame_idx, normals)
     if rank == 0:
         print(f"Rendered {len(theta)} frames to {output_dir}")
 
@@ -266,6 +282,14 @@ def write_acc(output_dir, frame_idx, acc):
     from PIL import Image
     img = (acc.clamp(0.0, 1.0) * 255).cpu().numpy().astype(np.uint8)
     Image.fromarray(img, mode='L').save(os.path.join(output_dir, f'acc_{frame_idx:03d}.png'))
+
+
+def write_normals(output_dir, frame_idx, normals):
+    """normal_{i:03d}.png beside the depth: the normal map (H,W,3), components in [-1, 1], as
+    uint8(255 clip(0.5 + 0.5 n, 0, 1)) by truncation like the rgb image; an empty ray is mid-grey."""
+    from PIL import Image
+    img = ((0.5 + 0.5 * normals).clamp(0.0, 1.0) * 255).cpu().numpy().astype(np.uint8)
+    Image.fromarray(img).save(os.path.join(output_dir, f'normal_{frame_idx:03d}.png'))
 
 
 def model_dimension_check(config):
@@ -374,7 +398,8 @@ def main(argv=None):
                     hierarchical=args.hierarchical, n_importance=args.n_importance, chunk=args.chunk,
                     seed=args.seed, shader=shader, occupancy=occupancy,
                     **{k: v for k, v in (("background", args.background), ("background_depth", args.background_depth))
-                       if v is not None}, **({"save_acc": True} if args.save_acc else {}))
+                       if v is not None}, **({"save_acc": True} if args.save_acc else {}),
+                    **({"save_normals": True} if args.save_normals else {}))
     if group is not None:
         dist.destroy_process_group()
     return 0
